@@ -20,6 +20,11 @@ Synthetic data / random-init weights of the full-size model.
     python bench.py --impl torch                      # stock torch DDP + torch.optim baseline
     python bench.py --model gpt2                      # GPT-2-small + grad accumulation (config #5)
     python bench.py --model bert                      # BERT-base pre-training (config #3)
+    python bench.py --dump-outputs DIR                # + the last timed step's loss as DIR/loss.npy
+    python bench.py --gpus 8 --full                   # + comm_diag: 3 untimed steps with device comm timing on
+
+A plain run sets up, warms up, times the steps and prints the JSON line;
+measurements that take steps of their own run only with --full.
 """
 from __future__ import annotations
 
@@ -95,6 +100,12 @@ def parse():
                     help="gloo: the reference's literal backend (main.py:50) — GPU tensors staged through the "
                          "host; ours = the C++ host communicator, stock = torch's gloo")
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: at N > 1 (and under --emulate-world) the "
+                         "3 untimed comm_diag steps after the timed ones")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32): "
+                         "loss.npy")
     ap.add_argument("--comm-timing", type=int, default=0,
                     help="record per-bucket device comm time + exposed (un-overlapped) comm ms in the JSON")
     ap.add_argument("--bucket-sweep", default=None,
@@ -164,6 +175,21 @@ def _self_launch(a) -> int:
     log(f"[bench] self-launching {a.gpus} ranks")
     return mod.launch_env([sys.executable, os.path.abspath(__file__)] + sys.argv[1:], a.gpus,
                           master_addr="127.0.0.1")
+
+
+def _dump_outputs(dirname, loss):
+    """What a caller of the timed step receives from its last call: the loss
+    the step returns, as ``loss.npy`` (float32, shape [1]). The parameters and
+    gradients the step leaves behind are not written: the kernels sum the BN
+    statistics with fp32 atomics and bf16 rounding spreads that, so from these
+    random-init weights they do not repeat even within one process (ResNet-50,
+    same weights and batch twice: the median parameter's gradient differs by
+    a relative L2 of about 1, the loss by 2.5e-4; README "bench.py
+    contract"), and cannot tell two builds apart."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "loss.npy"), loss.detach().to("cpu", torch.float32).reshape(1).numpy())
 
 
 def _heartbeat(period=30.0):
@@ -358,9 +384,11 @@ def main():
         ms = elapsed / a.steps * 1000.0
         samples_per_step = wl.per_gpu_batch * wl.accum * world
         total = samples_per_step * a.steps / elapsed
+        if a.dump_outputs and rank == 0:
+            _dump_outputs(a.dump_outputs, loss)
         rec = None
         diag = None
-        if ours and (world > 1 or a.emulate_world) and not a.comm_timing and not a.graph:
+        if a.full and ours and (world > 1 or a.emulate_world) and not a.comm_timing and not a.graph:
             # untimed diagnostic steps with device comm timing on: whether
             # overlap held (exposed vs per-bucket comm ms), as a multi-GPU run
             # record must be able to explain itself; MAX over ranks

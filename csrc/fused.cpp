@@ -1148,7 +1148,17 @@ kern::AttnParams attn_params(const at::Tensor& q, int64_t heads, bool causal, do
   p.p_drop = static_cast<float>(p_drop);
   p.seed = static_cast<uint64_t>(seed);
   p.mask = nullptr;
+  p.kmask = nullptr;
   return p;
+}
+// the packed key mask of attn_pack_key_mask for this (B, T), or none
+const uint64_t* attn_kmask(const c10::optional<at::Tensor>& km, const at::Tensor& q, const kern::AttnParams& p,
+                           const char* what) {
+  if (!km.has_value() || !km->defined()) return nullptr;
+  DK_CHECK(km->is_cuda() && km->device() == q.device() && km->scalar_type() == at::kLong && km->is_contiguous() &&
+               km->dim() == 2 && km->size(0) == p.B && km->size(1) == 1 + p.T / 64,
+           what, ": key_mask must be the contiguous int64 [B, 1 + T/64] tensor of attn_pack_key_mask on q's device");
+  return reinterpret_cast<const uint64_t*>(km->data_ptr<int64_t>());
 }
 void same_shape(const at::Tensor& a, const at::Tensor& b, const char* what) {
   DK_CHECK(a.sizes() == b.sizes(), what, ": shape mismatch");
@@ -1159,14 +1169,35 @@ bool attn_ok(int64_t T, int64_t C, int64_t heads) {
   return heads > 0 && C == heads * 64 && kern::attn_supported(static_cast<int>(T), 64);
 }
 
+// Key-padding mask [B, T] (bool / uint8, non-zero = the key takes part) ->
+// the packed int64 [B, 1 + T/64] the attention kernels read: per batch row the
+// count of leading 64-key blocks to visit, then one bit word per block. Built
+// on the device, no host sync (usable inside a captured step).
+at::Tensor attn_pack_key_mask(const at::Tensor& mask) {
+  DK_CHECK(mask.is_cuda() && mask.dim() == 2 && mask.is_contiguous() &&
+               (mask.scalar_type() == at::kBool || mask.scalar_type() == at::kByte),
+           "attn_pack_key_mask: contiguous bool / uint8 [B, T] mask on the GPU required");
+  const int64_t B = mask.size(0), T = mask.size(1);
+  DK_CHECK(B > 0 && B < (int64_t(1) << 31) && kern::attn_supported(static_cast<int>(T), 64),
+           "attn_pack_key_mask: T must be a multiple of 64 (at most 8192)");
+  c10::hip::HIPGuard guard(mask.device().index());
+  at::Tensor packed = at::empty({B, 1 + T / 64}, mask.options().dtype(at::kLong));
+  kern::attn_pack_key_mask(static_cast<const uint8_t*>(mask.data_ptr()),
+                           reinterpret_cast<uint64_t*>(packed.data_ptr<int64_t>()), static_cast<int>(B),
+                           static_cast<int>(T), stream_of(mask));
+  return packed;
+}
+
 // o [B, T, H*64] (contiguous), lse [B*H, T] fp32 (log2 domain), keep bits
 // (int32 [attn_mask_words], T²/8 bytes per head; empty without dropout)
 std::vector<at::Tensor> flash_attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, int64_t heads,
-                                       bool causal, double p_drop, int64_t seed, bool keep_bits) {
+                                       bool causal, double p_drop, int64_t seed, bool keep_bits,
+                                       const c10::optional<at::Tensor>& key_mask) {
   same_shape(q, k, "flash_attn_fwd");
   same_shape(q, v, "flash_attn_fwd");
   c10::hip::HIPGuard guard(q.device().index());
   kern::AttnParams p = attn_params(q, heads, causal, p_drop, seed);
+  p.kmask = attn_kmask(key_mask, q, p, "flash_attn_fwd");
   at::Tensor o = at::empty(q.sizes(), q.options().memory_format(at::MemoryFormat::Contiguous));
   at::Tensor lse = at::empty({q.size(0) * heads, q.size(1)}, q.options().dtype(at::kFloat));
   // the keep bits only when a backward will read them (T²/8 bytes per head)
@@ -1181,11 +1212,13 @@ std::vector<at::Tensor> flash_attn_fwd(const at::Tensor& q, const at::Tensor& k,
 // writes dq, dk, dv (strided views allowed, e.g. slices of one packed buffer)
 void flash_attn_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                     const at::Tensor& o, const at::Tensor& lse, const at::Tensor& mask, int64_t heads, bool causal,
-                    double p_drop, int64_t seed, at::Tensor& dq, at::Tensor& dk, at::Tensor& dv) {
+                    double p_drop, int64_t seed, at::Tensor& dq, at::Tensor& dk, at::Tensor& dv,
+                    const c10::optional<at::Tensor>& key_mask) {
   for (const at::Tensor* t : std::initializer_list<const at::Tensor*>{&k, &v, &o, &dout, &dq, &dk, &dv})
     same_shape(q, *t, "flash_attn_bwd");
   c10::hip::HIPGuard guard(q.device().index());
   kern::AttnParams p = attn_params(q, heads, causal, p_drop, seed);
+  p.kmask = attn_kmask(key_mask, q, p, "flash_attn_bwd");
   DK_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous() && lse.numel() == q.size(0) * heads * q.size(1),
             "flash_attn_bwd: lse");
   if (p.p_drop > 0.f) {  // the forward's keep bits
@@ -1832,8 +1865,16 @@ void bind(pybind11::module& m) {
         pybind11::arg("accumulate_into") = pybind11::none());
   m.def("flash_attn_fwd", &flash_attn_fwd, "MFMA flash attention forward (head dim 64)", pybind11::arg("q"),
         pybind11::arg("k"), pybind11::arg("v"), pybind11::arg("heads"), pybind11::arg("causal"),
-        pybind11::arg("p_drop"), pybind11::arg("seed"), pybind11::arg("keep_bits") = true);
-  m.def("flash_attn_bwd", &flash_attn_bwd, "MFMA flash attention backward into dq/dk/dv");
+        pybind11::arg("p_drop"), pybind11::arg("seed"), pybind11::arg("keep_bits") = true,
+        pybind11::arg("key_mask") = pybind11::none());
+  m.def("flash_attn_bwd", &flash_attn_bwd, "MFMA flash attention backward into dq/dk/dv", pybind11::arg("dout"),
+        pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"), pybind11::arg("o"), pybind11::arg("lse"),
+        pybind11::arg("keep"), pybind11::arg("heads"), pybind11::arg("causal"), pybind11::arg("p_drop"),
+        pybind11::arg("seed"), pybind11::arg("dq"), pybind11::arg("dk"), pybind11::arg("dv"),
+        pybind11::arg("key_mask") = pybind11::none());
+  m.def("attn_pack_key_mask", &attn_pack_key_mask,
+        "bool [B, T] key-padding mask -> packed int64 [B, 1 + T/64] for flash_attn_fwd / flash_attn_bwd",
+        pybind11::arg("mask"));
   m.def("conv_fwd", &conv_fwd, "kxk NHWC conv forward (implicit-GEMM MFMA) [+ output BN sums]", pybind11::arg("x"),
         pybind11::arg("wt"), pybind11::arg("kh"), pybind11::arg("kw"), pybind11::arg("stride"), pybind11::arg("pad"),
         pybind11::arg("stats") = false);

@@ -21,6 +21,23 @@
 //  * dropout: the forward hashes, and stores the keep decisions as bits (T²/8
 //    bytes per head, in a word order both backward kernels read directly);
 //    the backward hashes nothing.
+//  * key-padding mask (KMASK instantiations; the others carry no mask code):
+//    one 64-bit word per (batch, 64-key block), bit j = key 64·block + j takes
+//    part, and a per-batch count of leading blocks to visit, both built on the
+//    device by attn_pack_kernel and read at wave-uniform addresses.
+//    The semantics are SDPA's boolean attn_mask [B, 1, 1, T]: a hidden key is
+//    excluded from the row max, the normaliser and P·V (its raw score is
+//    selected to -inf BEFORE the running max, so a hidden key with a large
+//    score cannot move it); padding positions as queries are computed like any
+//    other. Blocks past the count are neither staged nor computed, an empty
+//    block inside is skipped after the barrier (the ring cadence is that of
+//    the causal early-out). The dropout hash does not depend on the mask.
+//    A row with no visible key (a fully hidden sequence, left padding under
+//    the causal mask, …) keeps m = -inf, l = 0: its output row is exactly 0 and
+//    its lse is stored as +inf (the FlashAttention-2 choice), so the backward's
+//    exp2(s·c − lse) is exactly 0 for every key of that row: dQ row 0, nothing
+//    added to dK / dV, δ = rowsum(dO ∘ O) = 0. Hidden keys of other rows get
+//    p = 0 by a select (their exp2 may overflow), so their dK / dV rows are 0.
 //
 // Replaces PyTorch-ROCm's scaled_dot_product_attention (aotriton Triton
 // kernels) on the BERT-base / GPT-2-small paths ("flash-style
@@ -245,6 +262,15 @@ __device__ __forceinline__ float sum_xor32(float x) {
   return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 
+// a wave-uniform 64-bit value into scalar registers (a key-mask word loaded
+// inside the tile loop comes back in vector registers: after the DMA asm's
+// memory clobber hipcc no longer selects a scalar load for it)
+__device__ __forceinline__ uint64_t uniform64(uint64_t x) {
+  const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x));
+  const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x >> 32));
+  return (static_cast<uint64_t>(hi) << 32) | lo;
+}
+
 // (batch-head, tile) of this workgroup. Causal: tiles carry unequal work
 // (query tile t of the forward / dQ sees t + 1 key tiles; key tile t of dK/dV
 // is seen by nt - t query tiles). Workgroups are dispatched breadth-first, so
@@ -282,7 +308,7 @@ __device__ __forceinline__ Ptrs head(const AttnTensor& t, int b, int hd) {
 }
 
 // ------------------------------------------------------------ forward ----
-template <bool CAUSAL, bool DROP>
+template <bool CAUSAL, bool DROP, bool KMASK>
 __global__ void __launch_bounds__(kT) attn_fwd_kernel(AttnParams P, AttnTensor q, AttnTensor k, AttnTensor v,
                                                       AttnOut o, float* __restrict__ lse) {
   __shared__ __attribute__((aligned(16))) char lds[2 * 2 * kTile];  // [ring][K | V]
@@ -316,6 +342,17 @@ __global__ void __launch_bounds__(kT) attn_fwd_kernel(AttnParams P, AttnTensor q
   f32x16 oacc[2] = {zero16(), zero16()};
   int nkb = T / kKB;
   if (CAUSAL) nkb = min(nkb, (tile * 128 + 128 + kKB - 1) / kKB);
+  // key mask: this batch's block count and words (wave-uniform addresses; kept
+  // in scalar registers, uniform64), the word one block ahead, its load issued
+  // in front of the next tile's DMA and used after the next wait. Blocks past
+  // the count are not staged.
+  const uint64_t* KM = nullptr;
+  uint64_t kwnext = 0;
+  if (KMASK) {
+    KM = P.kmask + static_cast<int64_t>(b) * (T / kKB + 1);
+    nkb = min(nkb, static_cast<int>(KM[0]));
+    kwnext = KM[1];
+  }
 
   const TileOff ko = tile_off(K.st, wave, lane), vo = tile_off(V.st, wave, lane);
   auto issue = [&](int it) {
@@ -328,12 +365,20 @@ __global__ void __launch_bounds__(kT) attn_fwd_kernel(AttnParams P, AttnTensor q
   for (int it = 0; it < nkb; ++it) {
     wait_vm0();
     barrier();
+    uint64_t kw = 0;
+    if (KMASK) {
+      kw = uniform64(kwnext);
+      kwnext = KM[1 + min(it + 1, nkb - 1)];
+    }
     issue(it + 1);
     const char* sK = lds + (it & 1) * 2 * kTile;
     const char* sV = sK + kTile;
     const int kb = it * kKB;
     // causal: a key block wholly after this wave's last query contributes nothing
     if (CAUSAL && kb > tile * 128 + wave * 32 + 31) continue;
+    // key mask: so does a block without a visible key (after the barrier and
+    // the next tile's issue, as the causal early-out: the ring cadence stays)
+    if (KMASK && kw == 0) continue;
     f32x16 s[2];
 #pragma unroll
     for (int kh = 0; kh < 2; ++kh) {
@@ -354,15 +399,30 @@ __global__ void __launch_bounds__(kT) attn_fwd_kernel(AttnParams P, AttnTensor q
           s[kh][r] = key > qi ? -INFINITY : s[kh][r];
         }
     }
+    // key mask on the raw scores, before the max (a hidden key with a large
+    // score must not move it); only on blocks that hide some key (wave-uniform)
+    if (KMASK && kw != ~0ull) {
+#pragma unroll
+      for (int kh = 0; kh < 2; ++kh) {
+        const uint32_t wl = static_cast<uint32_t>(kw >> (32 * kh)) >> (4 * hh);  // bit (r&3) + 8(r>>2): register r's key
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[kh][r] = ((wl >> ((r & 3) + 8 * (r >> 2))) & 1u) ? s[kh][r] : -INFINITY;
+      }
+    }
     float mx = m;
 #pragma unroll
     for (int kh = 0; kh < 2; ++kh)
 #pragma unroll
       for (int r = 0; r < 16; r += 2) mx = fmaxf(mx, fmaxf(s[kh][r], s[kh][r + 1]));
     mx = max_xor32(mx);
-    // (every wave's first block holds key 0 ≤ its queries: mx is finite from there on)
-    const float alpha = __builtin_amdgcn_exp2f((m - mx) * c);
-    const float nmc = -mx * c;
+    // (without a key mask every wave's first block holds key 0 ≤ its queries:
+    // mx is finite from there on. With one, a row that has seen no visible key
+    // yet has mx = -inf: its exponents are taken against 0, so alpha and every
+    // p are exp2(-inf) = 0, never (-inf) - (-inf))
+    float mxs = mx;
+    if (KMASK) mxs = mx == -INFINITY ? 0.f : mx;
+    const float alpha = __builtin_amdgcn_exp2f((m - mxs) * c);
+    const float nmc = -mxs * c;
     float rs = 0.f;  // without dropout: the row sum on the VALU (the 16 accumulator
                      // registers of the MFMA sum below would cost a wave per SIMD)
 #pragma unroll
@@ -422,7 +482,9 @@ __global__ void __launch_bounds__(kT) attn_fwd_kernel(AttnParams P, AttnTensor q
     if (DROP) l = l * alpha + lsum[0];
   }
   if (qok) {
-    const float inv = (DROP ? drop_scale(thr) : 1.f) / l;
+    // key mask: a row with no visible key has l = 0 (and O = 0): output row 0, lse +inf
+    const bool empty = KMASK && l == 0.f;
+    const float inv = empty ? 0.f : (DROP ? drop_scale(thr) : 1.f) / l;
     uint16_t* O = static_cast<uint16_t*>(o.ptr) + b * o.sb + hd * kD + static_cast<int64_t>(qi) * o.st;
 #pragma unroll
     for (int dh = 0; dh < 2; ++dh)
@@ -432,7 +494,7 @@ __global__ void __launch_bounds__(kT) attn_fwd_kernel(AttnParams P, AttnTensor q
         *reinterpret_cast<uint2*>(O + d0) = make_uint2(pack2(oacc[dh][4 * g] * inv, oacc[dh][4 * g + 1] * inv),
                                                        pack2(oacc[dh][4 * g + 2] * inv, oacc[dh][4 * g + 3] * inv));
       }
-    if (hh == 0) lse[static_cast<int64_t>(bh) * T + qi] = m * c + log2f(l);
+    if (hh == 0) lse[static_cast<int64_t>(bh) * T + qi] = empty ? INFINITY : m * c + log2f(l);
   }
 }
 
@@ -442,7 +504,7 @@ __global__ void __launch_bounds__(kT) attn_fwd_kernel(AttnParams P, AttnTensor q
 // δ = rowsum(dO ∘ O) is computed here from the query rows' dO (already loaded)
 // and O (4 more 16-B loads per lane, behind the first K/V stage), and stored
 // for the dK/dV kernel, which runs after this one (no separate δ pass).
-template <bool CAUSAL, bool DROP>
+template <bool CAUSAL, bool DROP, bool KMASK>
 __global__ void __launch_bounds__(kT) attn_bwd_dq_kernel(AttnParams P, AttnTensor q, AttnTensor k, AttnTensor v,
                                                          AttnTensor dout, AttnTensor o, const float* __restrict__ lse,
                                                          float* __restrict__ delta, AttnOut dq) {
@@ -491,7 +553,17 @@ __global__ void __launch_bounds__(kT) attn_bwd_dq_kernel(AttnParams P, AttnTenso
   f32x16 dacc[2] = {zero16(), zero16()};
   int nkb = T / kKB;
   if (CAUSAL) nkb = min(nkb, (tile * 128 + 128 + kKB - 1) / kKB);
+  // key mask: block count and words as in the forward (one block ahead)
+  const uint64_t* KM = nullptr;
+  uint64_t kwnext = 0;
+  if (KMASK) {
+    KM = P.kmask + static_cast<int64_t>(b) * (T / kKB + 1);
+    nkb = min(nkb, static_cast<int>(KM[0]));
+    kwnext = KM[1];
+  }
   // this lane's keep words (one per key block, stride 2T), one block ahead
+  // (key mask: the words of blocks the forward skipped were never written;
+  // they are loaded and never used)
   const uint32_t* MW = P.mask + mask_word(bh, T / kKB, 0, hh, T, qok ? qi : 0);
   uint32_t wnext = DROP ? MW[0] : 0u;
   const TileOff ko = tile_off(K.st, wave, lane), vo = tile_off(V.st, wave, lane);
@@ -509,12 +581,18 @@ __global__ void __launch_bounds__(kT) attn_bwd_dq_kernel(AttnParams P, AttnTenso
     // the word's use (hence hipcc's vmcnt wait for it) here, where nothing
     // else is in flight — not after the next tile's DMA is issued
     if (DROP) asm volatile("" ::"v"(w));
+    uint64_t kw = 0;
+    if (KMASK) {
+      kw = uniform64(kwnext);
+      kwnext = KM[1 + min(it + 1, nkb - 1)];
+    }
     issue(it + 1);
     if (DROP) wnext = MW[static_cast<int64_t>(min(it + 1, nkb - 1)) * 2 * T];
     const char* sK = lds + (it & 1) * 2 * kTile;
     const char* sV = sK + kTile;
     const int kb = it * kKB;
     if (CAUSAL && kb > tile * 128 + wave * 32 + 31) continue;
+    if (KMASK && kw == 0) continue;  // no visible key in the block (as the forward)
     // one 32-key half at a time: issuing both halves' S / dP first (as dK/dV
     // does) took the kernel from 152 to 197 registers, three waves per SIMD to
     // two, and measured slower (GPT-2 43.1 → 45.7 µs, NOTES §28)
@@ -529,11 +607,17 @@ __global__ void __launch_bounds__(kT) attn_bwd_dq_kernel(AttnParams P, AttnTenso
       const uint32_t wk = w >> (4 * kh);  // key 8g + 4hh + e of this half at bit 8e + g
       // causal mask only where this 32-key half reaches past the wave's first query
       const bool diag = CAUSAL && kb + 32 * kh + 31 > tile * 128 + wave * 32;
+      // key mask: this half's 32 bits, register r's key at bit (r&3) + 8(r>>2);
+      // the select only where the half hides some key (wave-uniform)
+      const uint32_t kwh = KMASK ? static_cast<uint32_t>(kw >> (32 * kh)) : ~0u;
+      const bool hid = KMASK && kwh != ~0u;
+      const uint32_t wl = kwh >> (4 * hh);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int key = kb + 32 * kh + (r & 3) + 8 * (r >> 2) + 4 * hh;
         float p = __builtin_amdgcn_exp2f(fmaf(s[r], c, -lse2));
         if (CAUSAL && diag) p = key > qi ? 0.f : p;
+        if (KMASK && hid) p = ((wl >> ((r & 3) + 8 * (r >> 2))) & 1u) ? p : 0.f;
         float g = dp[r];
         if (DROP) {
           uint32_t km;
@@ -576,7 +660,7 @@ __global__ void __launch_bounds__(kT) attn_bwd_dq_kernel(AttnParams P, AttnTenso
 // key on the lane: S = Q·Kᵀ, dP = dO·Vᵀ (queries in the accumulator rows),
 // dVᵀ += dOᵀ·(P∘keep/(1-p)), dKᵀ += Qᵀ·dS. Q / dO tiles (+ LSE, δ) stream
 // through LDS; each wave keeps its 32 keys' dKᵀ, dVᵀ in registers.
-template <bool CAUSAL, bool DROP>
+template <bool CAUSAL, bool DROP, bool KMASK>
 __global__ void __launch_bounds__(kT) attn_bwd_dkv_kernel(AttnParams P, AttnTensor q, AttnTensor k, AttnTensor v,
                                                           AttnTensor dout, const float* __restrict__ lse,
                                                           const float* __restrict__ delta, AttnOut dk, AttnOut dv) {
@@ -595,6 +679,35 @@ __global__ void __launch_bounds__(kT) attn_bwd_dkv_kernel(AttnParams P, AttnTens
   const int key = kb0 + wave * 32 + (lane & 31);  // this lane's key
   const bool kok = key < T;
   const Ptrs Q = head(q, b, hd), K = head(k, b, hd), V = head(v, b, hd), G = head(dout, b, hd);
+  // key mask: the tile's two words (key blocks kb0/64 and, inside T, the next;
+  // scalar loads); this wave's 32 keys are bits 32(wave&1)… of word wave>>1.
+  // A hidden key's lane forces p = 0 for every query below: its dK / dV rows
+  // come out as exact zeros whatever the (possibly never written) keep words
+  // of its block hold. A tile without a visible key writes zeros right here.
+  uint32_t wvis = ~0u;
+  bool vis = true;
+  if (KMASK) {
+    const uint64_t* KM = P.kmask + static_cast<int64_t>(b) * (T / kKB + 1) + 1 + kb0 / kKB;
+    const uint64_t w0 = KM[0];
+    const uint64_t w1 = kb0 + kKB < T ? KM[1] : 0ull;
+    if ((w0 | w1) == 0) {
+      if (kok) {
+        uint16_t* DK = static_cast<uint16_t*>(dk.ptr) + b * dk.sb + hd * kD + static_cast<int64_t>(key) * dk.st;
+        uint16_t* DV = static_cast<uint16_t*>(dv.ptr) + b * dv.sb + hd * kD + static_cast<int64_t>(key) * dv.st;
+#pragma unroll
+        for (int dh = 0; dh < 2; ++dh)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const int d0 = 32 * dh + 8 * g + 4 * hh;
+            *reinterpret_cast<uint2*>(DK + d0) = make_uint2(0u, 0u);
+            *reinterpret_cast<uint2*>(DV + d0) = make_uint2(0u, 0u);
+          }
+      }
+      return;
+    }
+    wvis = static_cast<uint32_t>(((wave >> 1) ? w1 : w0) >> (32 * (wave & 1)));
+    vis = (wvis >> (lane & 31)) & 1u;
+  }
   bf16x8 kf[4], vf[4];
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) {
@@ -658,6 +771,7 @@ __global__ void __launch_bounds__(kT) attn_bwd_dkv_kernel(AttnParams P, AttnTens
     // either way). Sub-tiles that precede every key of this wave skip their
     // VALU and dV / dK MFMAs (the diagonal tiles only).
     if (CAUSAL && qb + 63 < kb0 + wave * 32) continue;  // every query of the tile precedes every key
+    if (KMASK && wvis == 0) continue;                   // none of this wave's keys is visible: dK = dV = 0
     f32x16 s[2], dp[2];
 #pragma unroll
     for (int qs = 0; qs < 2; ++qs) {
@@ -702,6 +816,7 @@ __global__ void __launch_bounds__(kT) attn_bwd_dkv_kernel(AttnParams P, AttnTens
             const int qrow = qb + rl + e;
             float p = __builtin_amdgcn_exp2f(fmaf(s[qs][r], c, -lv[e]));
             if (CAUSAL && diag) p = key > qrow ? 0.f : p;
+            if (KMASK && wvis != ~0u) p = vis ? p : 0.f;  // only in waves that hold a hidden key
             float gg = dp[qs][r], pk = p;
             if (DROP) {
               gg = and_mask(gg, km[e]);
@@ -742,19 +857,59 @@ __global__ void __launch_bounds__(kT) attn_bwd_dkv_kernel(AttnParams P, AttnTens
   }
 }
 
+// ------------------------------------------------- key-mask packer -------
+// mask [B][T] bytes -> packed [B][1 + T/64] uint64 (AttnParams::kmask). One
+// workgroup per batch row; each wave ballots 64 keys at a time into one word
+// and remembers its last non-empty block; lane 0 of wave 0 combines the four
+// into the block count. No host sync: usable inside a captured step.
+__global__ void __launch_bounds__(kT) attn_pack_kernel(const uint8_t* __restrict__ mask,
+                                                       uint64_t* __restrict__ packed, int T) {
+  __shared__ int last[kT / 64];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int nblk = T / kKB;
+  const uint8_t* M = mask + static_cast<int64_t>(blockIdx.x) * T;
+  uint64_t* W = packed + static_cast<int64_t>(blockIdx.x) * (nblk + 1);
+  int cnt = 0;  // 1 + this wave's last block with a visible key
+  for (int blk = wave; blk < nblk; blk += kT / 64) {
+    const uint64_t w = __ballot(M[blk * kKB + lane] != 0);
+    if (lane == 0) W[1 + blk] = w;
+    if (w != 0) cnt = blk + 1;
+  }
+  if (lane == 0) last[wave] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int n = 0;
+#pragma unroll
+    for (int i = 0; i < kT / 64; ++i) n = max(n, last[i]);
+    W[0] = static_cast<uint64_t>(n);
+  }
+}
+
 }  // namespace
 
 bool attn_supported(int T, int D) { return D == kD && T > 0 && T % kKB == 0 && T <= 8192; }  // 13-bit query in the dropout counter
+
+void attn_pack_key_mask(const uint8_t* mask, uint64_t* packed, int B, int T, hipStream_t s) {
+  hipLaunchKernelGGL(attn_pack_kernel, dim3(B), dim3(kT), 0, s, mask, packed, T);
+}
 
 void attn_fwd(const AttnParams& p, AttnTensor q, AttnTensor k, AttnTensor v, AttnOut o, float* lse,
               hipStream_t s) {
   const dim3 grid(p.B * p.H, (p.T + 127) / 128);
   const bool drop = p.p_drop > 0.f;
-#define DK_AF(C, D) hipLaunchKernelGGL((attn_fwd_kernel<C, D>), grid, dim3(kT), 0, s, p, q, k, v, o, lse)
-  if (p.causal && drop) DK_AF(true, true);
-  else if (p.causal) DK_AF(true, false);
-  else if (drop) DK_AF(false, true);
-  else DK_AF(false, false);
+  const bool km = p.kmask != nullptr;
+#define DK_AF(C, D, M) hipLaunchKernelGGL((attn_fwd_kernel<C, D, M>), grid, dim3(kT), 0, s, p, q, k, v, o, lse)
+#define DK_AFM(C, D)         \
+  do {                       \
+    if (km) DK_AF(C, D, true); \
+    else DK_AF(C, D, false); \
+  } while (0)
+  if (p.causal && drop) DK_AFM(true, true);
+  else if (p.causal) DK_AFM(true, false);
+  else if (drop) DK_AFM(false, true);
+  else DK_AFM(false, false);
+#undef DK_AFM
 #undef DK_AF
 }
 
@@ -763,15 +918,22 @@ void attn_bwd(const AttnParams& p, AttnTensor q, AttnTensor k, AttnTensor v, Att
   // dQ first: it computes δ = rowsum(dO ∘ O) on the way and stores it for dK/dV
   const dim3 grid(p.B * p.H, (p.T + 127) / 128);
   const bool drop = p.p_drop > 0.f;
-#define DK_AB(C, D)                                                                                             \
-  do {                                                                                                           \
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<C, D>), grid, dim3(kT), 0, s, p, q, k, v, dout, o, lse, delta, dq);   \
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<C, D>), grid, dim3(kT), 0, s, p, q, k, v, dout, lse, delta, dk, dv); \
+  const bool km = p.kmask != nullptr;
+#define DK_AB(C, D, M)                                                                                             \
+  do {                                                                                                              \
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<C, D, M>), grid, dim3(kT), 0, s, p, q, k, v, dout, o, lse, delta, dq);   \
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<C, D, M>), grid, dim3(kT), 0, s, p, q, k, v, dout, lse, delta, dk, dv); \
   } while (0)
-  if (p.causal && drop) DK_AB(true, true);
-  else if (p.causal) DK_AB(true, false);
-  else if (drop) DK_AB(false, true);
-  else DK_AB(false, false);
+#define DK_ABM(C, D)         \
+  do {                       \
+    if (km) DK_AB(C, D, true); \
+    else DK_AB(C, D, false); \
+  } while (0)
+  if (p.causal && drop) DK_ABM(true, true);
+  else if (p.causal) DK_ABM(true, false);
+  else if (drop) DK_ABM(false, true);
+  else DK_ABM(false, false);
+#undef DK_ABM
 #undef DK_AB
 }
 

@@ -7,8 +7,10 @@ next-sentence prediction. Random init (std 0.02).
 MI355X path: every LayerNorm is the hand-written kernel; the MLM head runs
 only on the masked positions (gathered first: ~15 % of tokens), and its
 vocab cross-entropy is the fused kernel on bf16 logits; attention is our MFMA
-flash-attention kernel (``ops/attention.py``; ``scaled_dot_product_attention``
-when a padding mask is given or with ``fused=False``).
+flash-attention kernel (``ops/attention.py``), with or without a padding mask
+(``attention_mask`` is packed to bits once per forward and every layer's
+kernels skip the padding; ``scaled_dot_product_attention`` with ``fused=False``,
+on the CPU, in fp32 and for unsupported shapes).
 """
 from __future__ import annotations
 
@@ -18,7 +20,7 @@ import torch
 from torch import nn
 from torch.nn import functional as F
 
-from ..ops.attention import attn_supported, flash_attn_qkv
+from ..ops.attention import attn_shape_supported, attn_supported, flash_attn_qkv, pack_key_mask
 from ..ops.embedding import FusedEmbedding
 from ..ops.linear import FusedLinear, LinearWeightPrep, fused_mlp_gelu, packed_linear
 from ..ops.lm_head import lm_head_cross_entropy, padded_vocab
@@ -60,15 +62,23 @@ class BertSelfAttention(nn.Module):
         self.dropout = cfg.dropout
         self.fused = cfg.fused
 
-    def forward(self, x, mask):
+    def forward(self, x, mask, key_mask=None):
+        """``mask``: the boolean [B, 1, 1, T] padding mask for the SDPA path (or
+        None); ``key_mask``: the same mask packed for the flash kernels by
+        ``pack_key_mask`` (BertForPreTraining packs it once per forward when
+        the flash path will be taken), which then run masked inputs too."""
         B, T, C = x.shape
         h = self.heads
-        if self.fused and mask is None:
+        if self.fused and (mask is None or key_mask is not None):
             # query / key / value as one packed GEMM (one dgrad GEMM, no
             # per-projection gradient adds) feeding the packed MFMA flash attention
             qkv = packed_linear(x, (self.query, self.key, self.value))
             if attn_supported(qkv[..., :C], h):
-                return flash_attn_qkv(qkv, h, causal=False, dropout_p=self.dropout if self.training else 0.0)
+                return flash_attn_qkv(qkv, h, causal=False, dropout_p=self.dropout if self.training else 0.0,
+                                      key_mask=key_mask)
+            if key_mask is not None:
+                raise RuntimeError("BertSelfAttention: a packed key mask was given for a shape / dtype the flash "
+                                   "attention kernels do not take")
             q, k, v = qkv.split(C, dim=2)
             return F.scaled_dot_product_attention(
                 q.view(B, T, h, C // h).transpose(1, 2), k.view(B, T, h, C // h).transpose(1, 2),
@@ -96,19 +106,20 @@ class BertLayer(nn.Module):
         self.p = cfg.dropout
         self._dadd = dropout_add if cfg.fused else _plain_dropout_add
 
-    def forward(self, x, mask, x_res=None, dual_out: bool = False):
-        """``x_res``: an alias of ``x`` for the residual add (the previous
+    def forward(self, x, mask, x_res=None, dual_out: bool = False, key_mask=None):
+        """``key_mask``: the padding mask packed for the flash attention (see
+        BertSelfAttention). ``x_res``: an alias of ``x`` for the residual add (the previous
         layer's dual-output LN), ``dual_out``: return (y, alias of y). With the
         fused LNs every post-LN output's two gradients (next sublayer + its
         residual add) are summed inside the LN backward instead of by an add."""
         dual = isinstance(self.attn_ln, FusedLayerNorm)
         x_res = x if x_res is None else x_res
         fuse = dual and ln_mod.FUSE_DADD_LN
+        a = self.attn_out(self.attention(x, mask, key_mask))
         if fuse:  # residual dropout-add inside the LayerNorm kernels (ops.layernorm.dropout_add_layer_norm)
-            x, xa = dropout_add_layer_norm(self.attn_out(self.attention(x, mask)), x_res, self.attn_ln, self.p,
-                                           self.training, 2)
+            x, xa = dropout_add_layer_norm(a, x_res, self.attn_ln, self.p, self.training, 2)
         else:
-            h = self._dadd(self.attn_out(self.attention(x, mask)), x_res, self.p, self.training)
+            h = self._dadd(a, x_res, self.p, self.training)
             x, xa = self.attn_ln.forward_dual_out(h) if dual else (self.attn_ln(h), None)
         if isinstance(self.intermediate, FusedLinear):
             # one node: GELU in the first GEMM's epilogue, its backward in the second's dgrad epilogue
@@ -150,6 +161,16 @@ class BertForPreTraining(nn.Module):
         if isinstance(m, nn.Linear) and m.bias is not None:
             nn.init.zeros_(m.bias)
 
+    def _flash_attention(self, x) -> bool:
+        """Whether the layers' packed QKV projection of ``x`` feeds the flash
+        attention kernels: fused model, GPU, a bf16 projection (bf16 input or
+        bf16 autocast, as ``packed_linear`` decides) and a supported shape."""
+        if not (self.cfg.fused and x.is_cuda):
+            return False
+        bf16 = x.dtype == torch.bfloat16 or (torch.is_autocast_enabled("cuda")
+                                             and torch.get_autocast_dtype("cuda") == torch.bfloat16)
+        return bf16 and attn_shape_supported(x.shape[1], x.shape[2], self.cfg.heads)
+
     def forward(self, input_ids, token_type_ids=None, attention_mask=None, mlm_labels=None, nsp_labels=None,
                 mlm_positions=None):
         """``mlm_labels``: either [B, T] with -100 for unmasked tokens, or — with
@@ -168,15 +189,18 @@ class BertForPreTraining(nn.Module):
         x = self.word_embeddings(input_ids) + self.position_embeddings(pos) + self.token_type_embeddings(
             token_type_ids)
         x = self.emb_drop(self.emb_ln(x))
-        mask = None
+        mask = key_mask = None
         if attention_mask is not None:
             mask = attention_mask[:, None, None, :].to(torch.bool)
+            if self._flash_attention(x):
+                # packed once for all layers: the flash attention runs padded batches too
+                key_mask = pack_key_mask(attention_mask)
         xa = None
         for i, layer in enumerate(self.layers):
             if i + 1 < len(self.layers):
-                x, xa = layer(x, mask, xa, dual_out=True)
+                x, xa = layer(x, mask, xa, dual_out=True, key_mask=key_mask)
             else:
-                x = layer(x, mask, xa)
+                x = layer(x, mask, xa, key_mask=key_mask)
         pooled = torch.tanh(self.pooler(x[:, 0]))
         nsp_logits = self.nsp(pooled)
         if mlm_labels is None:

@@ -12,6 +12,20 @@ GPT-2-small and BERT-base.
   layout the output projection consumes (no head transposes).
 * :func:`flash_attn_qkv` — packed [B, T, 3*H*64] input (GPT-2's ``c_attn``);
   the backward writes dq/dk/dv straight into one packed gradient (no cat).
+* :func:`pack_key_mask` — a [B, T] key-padding mask as the bits the kernels
+  read (``key_mask=`` of both functions).
+
+Key-padding mask. ``key_mask`` has the semantics of a boolean ``attn_mask`` of
+shape [B, 1, 1, T] in ``scaled_dot_product_attention``: True means the key
+takes part. A hidden key is excluded from the row max, the softmax normaliser
+and P·V, and its dK / dV rows are exactly 0; padding positions as *queries*
+are computed like any other query. The dropout decisions do not depend on the
+mask. The kernels skip 64-key blocks without a visible key, and neither load
+nor compute the trailing ones. Zero-row rule: a query that sees no key at all
+(a fully hidden sequence, left padding under the causal mask) gets an output
+row of exactly 0 and a dQ row of exactly 0 and adds nothing to dK / dV — where
+a softmax over an empty set would give NaN. ``key_mask=None`` runs the kernels
+that carry no mask code.
 """
 from __future__ import annotations
 
@@ -25,45 +39,55 @@ def _seed() -> int:
     return int(torch.randint(0, 2**62, (1,), dtype=torch.int64).item())
 
 
+def attn_shape_supported(T: int, C: int, heads: int) -> bool:
+    """Whether the kernels take sequence length T with C = heads * 64 channels."""
+    return bool(_C.attn_ok(T, C, heads))
+
+
 def attn_supported(x: torch.Tensor, heads: int) -> bool:
     return (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 3
             and bool(_C.attn_ok(x.shape[1], x.shape[2], heads)))
 
 
+def _km_args(km):
+    # without a mask: exactly the _C calls (and kernels) of the unmasked op
+    return () if km is None else (km,)
+
+
 class _FlashAttnFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, heads, causal, p_drop, seed, keep_bits):
-        o, lse, keep = _C.flash_attn_fwd(q, k, v, heads, causal, p_drop, seed, keep_bits)
-        ctx.save_for_backward(q, k, v, o, lse, keep)
+    def forward(ctx, q, k, v, heads, causal, p_drop, seed, keep_bits, km):
+        o, lse, keep = _C.flash_attn_fwd(q, k, v, heads, causal, p_drop, seed, keep_bits, *_km_args(km))
+        ctx.save_for_backward(q, k, v, o, lse, keep, km)
         ctx.cfg = (heads, causal, p_drop, seed)
         return o
 
     @staticmethod
     def backward(ctx, do):
-        q, k, v, o, lse, keep = ctx.saved_tensors
+        q, k, v, o, lse, keep, km = ctx.saved_tensors
         heads, causal, p_drop, seed = ctx.cfg
         do = do.contiguous()
         if do.dtype != torch.bfloat16:
             do = do.to(torch.bfloat16)
         dq, dk, dv = torch.empty_like(q, memory_format=torch.contiguous_format), torch.empty_like(
             k, memory_format=torch.contiguous_format), torch.empty_like(v, memory_format=torch.contiguous_format)
-        _C.flash_attn_bwd(do, q, k, v, o, lse, keep, heads, causal, p_drop, seed, dq, dk, dv)
-        return dq, dk, dv, None, None, None, None, None
+        _C.flash_attn_bwd(do, q, k, v, o, lse, keep, heads, causal, p_drop, seed, dq, dk, dv, *_km_args(km))
+        return dq, dk, dv, None, None, None, None, None, None
 
 
 class _FlashAttnQKVFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, heads, causal, p_drop, seed, keep_bits):
+    def forward(ctx, qkv, heads, causal, p_drop, seed, keep_bits, km):
         C = qkv.shape[2] // 3
         q, k, v = qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:]
-        o, lse, keep = _C.flash_attn_fwd(q, k, v, heads, causal, p_drop, seed, keep_bits)
-        ctx.save_for_backward(qkv, o, lse, keep)
+        o, lse, keep = _C.flash_attn_fwd(q, k, v, heads, causal, p_drop, seed, keep_bits, *_km_args(km))
+        ctx.save_for_backward(qkv, o, lse, keep, km)
         ctx.cfg = (heads, causal, p_drop, seed)
         return o
 
     @staticmethod
     def backward(ctx, do):
-        qkv, o, lse, keep = ctx.saved_tensors
+        qkv, o, lse, keep, km = ctx.saved_tensors
         heads, causal, p_drop, seed = ctx.cfg
         do = do.contiguous()
         if do.dtype != torch.bfloat16:
@@ -72,21 +96,79 @@ class _FlashAttnQKVFn(torch.autograd.Function):
         dqkv = torch.empty_like(qkv, memory_format=torch.contiguous_format)
         q, k, v = qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:]
         dq, dk, dv = dqkv[..., :C], dqkv[..., C:2 * C], dqkv[..., 2 * C:]
-        _C.flash_attn_bwd(do, q, k, v, o, lse, keep, heads, causal, p_drop, seed, dq, dk, dv)
-        return dqkv, None, None, None, None, None
+        _C.flash_attn_bwd(do, q, k, v, o, lse, keep, heads, causal, p_drop, seed, dq, dk, dv, *_km_args(km))
+        return dqkv, None, None, None, None, None, None
+
+
+def pack_key_mask(mask: torch.Tensor) -> torch.Tensor:
+    """A key-padding mask [B, T] (bool, or an integer tensor of 0 / 1; T a
+    multiple of 64; non-zero = the key takes part) as the kernels read it:
+    int64 [B, 1 + T/64]. Per batch row, element 0 is the number of leading
+    64-key blocks to visit (1 + the index of the last block with a visible
+    key, 0 if there is none) and element 1 + j holds key block j, bit i (of
+    the 64-bit pattern) = key 64j + i. The layout is internal to this module
+    and the kernels. On the GPU a HIP kernel packs (no host sync, so it can be
+    captured); on the CPU the same layout is built with torch ops (the
+    packer's oracle)."""
+    if mask.dim() != 2 or mask.shape[1] == 0 or mask.shape[1] % 64 != 0:
+        raise ValueError(f"pack_key_mask: a [B, T] mask with T a multiple of 64 is required, got {tuple(mask.shape)}")
+    if mask.dtype.is_floating_point or mask.dtype.is_complex:
+        raise TypeError(f"pack_key_mask: bool or integer mask required, got {mask.dtype}")
+    if mask.dtype != torch.bool:
+        mask = mask != 0
+    if mask.is_cuda:
+        return _C.attn_pack_key_mask(mask.contiguous())
+    B, T = mask.shape
+    nblk = T // 64
+    bits = mask.view(B, nblk, 64).to(torch.int64)
+    # bit 63 is int64's sign bit: shifts wrap, the sum of distinct bits is their OR
+    words = (bits << torch.arange(64, dtype=torch.int64)).sum(-1)
+    count = ((words != 0).to(torch.int64) * torch.arange(1, nblk + 1, dtype=torch.int64)).amax(-1, keepdim=True)
+    return torch.cat([count, words], dim=1)
+
+
+def _packed_key_mask(key_mask, B: int, T: int):
+    """``key_mask`` of flash_attn / flash_attn_qkv as the packed tensor: the
+    result of :func:`pack_key_mask` is recognised by its dtype and shape
+    (int64 [B, 1 + T/64]; a [B, T] mask never has that shape: T ≥ 64 >
+    1 + T/64), anything else is a [B, T] mask and is packed here."""
+    if key_mask is None:
+        return None
+    if key_mask.dtype == torch.int64 and tuple(key_mask.shape) == (B, 1 + T // 64):
+        return key_mask
+    if tuple(key_mask.shape) != (B, T):
+        raise ValueError(f"key_mask: a [B, T] = [{B}, {T}] mask or its pack_key_mask() required, "
+                         f"got {tuple(key_mask.shape)}")
+    return pack_key_mask(key_mask)
 
 
 def flash_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, causal: bool = False,
-               dropout_p: float = 0.0, seed: int = None) -> torch.Tensor:
-    """softmax(q kᵀ / 8 [+ causal mask]) → dropout(p) → · v, per head of 64."""
+               dropout_p: float = 0.0, seed: int = None, key_mask: torch.Tensor = None) -> torch.Tensor:
+    """softmax(q kᵀ / 8 [+ causal mask] [+ key mask]) → dropout(p) → · v, per head of 64.
+
+    ``key_mask``: a [B, T] bool key-padding mask (True = the key takes part;
+    module docstring), packed on the spot by one small kernel, or the result
+    of :func:`pack_key_mask`. A model whose layers share one mask should pack
+    it once per forward and pass the packed tensor to every layer.
+
+    Under graph capture the op re-reads, on replay, the memory of the tensor
+    it was given. Given the bool mask, the packer is part of the captured
+    work: changing the mask's contents in place between replays changes the
+    result accordingly (forward and backward). Given a tensor packed outside
+    the capture, replays read those packed bits: later changes to the bool
+    mask they were made from are not seen."""
+    km = _packed_key_mask(key_mask, q.shape[0], q.shape[1])
     return _FlashAttnFn.apply(q, k, v, heads, causal, float(dropout_p), _seed() if seed is None else int(seed),
-                              _backward_will_run(q, k, v))
+                              _backward_will_run(q, k, v), km)
 
 
 def flash_attn_qkv(qkv: torch.Tensor, heads: int, causal: bool = False, dropout_p: float = 0.0,
-                   seed: int = None) -> torch.Tensor:
+                   seed: int = None, key_mask: torch.Tensor = None) -> torch.Tensor:
+    """:func:`flash_attn` on the three slices of a packed [B, T, 3*H*64]
+    projection (``key_mask`` as there)."""
+    km = _packed_key_mask(key_mask, qkv.shape[0], qkv.shape[1])
     return _FlashAttnQKVFn.apply(qkv, heads, causal, float(dropout_p), _seed() if seed is None else int(seed),
-                                 _backward_will_run(qkv))
+                                 _backward_will_run(qkv), km)
 
 
 def _backward_will_run(*ts) -> bool:

@@ -858,6 +858,62 @@ std::vector<at::Tensor> conv1x1_dgrad_resred(const at::Tensor& gy, const at::Ten
   return {g, acc, acc2};
 }
 
+// Backward of a bottleneck's conv3 with BN3's backward apply as the kernel's
+// prologue (conv3_bwd.hip): from the masked gradient g of BN3's output and
+// acc = (Σg, Σg·(z3 - mean3)), returns (dy2, acc2, dz3) — what bn_bwd_apply_g
+// followed by conv1x1_dgrad_bnred return, without the data-gradient GEMM's
+// re-read of dz3. wt = W3ᵀ bf16 [w][4w]; x2 / gamma2 … invstd2: BN2 (conv3's
+// input BN), as conv1x1_dgrad_bnred takes them.
+std::vector<at::Tensor> conv3_bwd_fused(const at::Tensor& g, const at::Tensor& z3, const at::Tensor& gamma3,
+                                        const at::Tensor& mean3, const at::Tensor& invstd3, const at::Tensor& acc3,
+                                        const at::Tensor& wt, const at::Tensor& x2,
+                                        const c10::optional<at::Tensor>& gamma2,
+                                        const c10::optional<at::Tensor>& beta2, const at::Tensor& mean2,
+                                        const at::Tensor& invstd2) {
+  check_gemm_act(g, "conv3_bwd_fused");
+  check_gemm_act(z3, "conv3_bwd_fused");
+  c10::hip::HIPGuard guard(g.device().index());
+  DK_CHECK(g.dim() == 4 && g.sizes() == z3.sizes(), "conv3_bwd_fused: g must match z3");
+  const int64_t C = g.size(1);
+  const int64_t M = g.numel() / C;
+  const int64_t w = C / 4;
+  DK_CHECK(C % 4 == 0 && kern::conv3_bwd_mode(M, static_cast<int>(w)) > 0, "conv3_bwd_fused: unsupported shape");
+  DK_CHECK(wt.scalar_type() == at::kBFloat16 && wt.is_contiguous() && wt.numel() == w * C,
+            "conv3_bwd_fused: weight must be contiguous bf16 [w][4w]");
+  auto f32c = [&](const at::Tensor& t, int64_t n) {
+    return t.scalar_type() == at::kFloat && t.numel() == n && t.is_contiguous() && t.device() == g.device();
+  };
+  DK_CHECK(f32c(gamma3, C) && f32c(mean3, C) && f32c(invstd3, C) && f32c(acc3, 2 * C),
+            "conv3_bwd_fused: BN3 gamma / mean / invstd fp32 [4w], acc fp32 [2*4w]");
+  DK_CHECK(f32c(invstd2, w), "conv3_bwd_fused: BN2 invstd fp32 [w]");
+  const BnRedIn r = bnred_in(x2, gamma2, beta2, mean2, invstd2, w, "conv3_bwd_fused");
+  DK_CHECK(x2.numel() == M * w && x2.size(0) == g.size(0), "conv3_bwd_fused: x2 / g pixel count mismatch");
+  at::Tensor dz3 = at::empty_like(z3, at::MemoryFormat::ChannelsLast);
+  at::Tensor dy2 = at::empty_like(x2, at::MemoryFormat::ChannelsLast);
+  auto s = stream_of(g);
+  at::Tensor acc2 = zeroed_floats(2 * w, g, s);
+  kern::conv3_bwd_bf16(g.data_ptr(), z3.data_ptr(), wt.data_ptr(), x2.data_ptr(), dz3.data_ptr(), dy2.data_ptr(), M,
+                       static_cast<int>(w), gamma3.data_ptr<float>(), mean3.data_ptr<float>(),
+                       invstd3.data_ptr<float>(), acc3.data_ptr<float>(),
+                       r.w.defined() ? r.w.data_ptr<float>() : nullptr,
+                       r.b.defined() ? r.b.data_ptr<float>() : nullptr, r.mean, r.invstd, acc2.data_ptr<float>(), s);
+  return {dy2, acc2, dz3};
+}
+
+// (dweight, dbias) of a training BN from acc = (Σg, Σg·(x - mean)) alone: the
+// values bn_bwd_apply_g returns, for a node whose apply pass runs later
+std::vector<at::Tensor> bn_dparams(const at::Tensor& acc, const at::Tensor& invstd) {
+  const int64_t C = invstd.numel();
+  DK_CHECK(acc.is_cuda() && acc.scalar_type() == at::kFloat && acc.numel() == 2 * C && acc.is_contiguous() &&
+                invstd.scalar_type() == at::kFloat && invstd.is_contiguous() && invstd.device() == acc.device(),
+            "bn_dparams: acc fp32 [2*C], invstd fp32 [C]");
+  c10::hip::HIPGuard guard(acc.device().index());
+  at::Tensor dw = at::empty({C}, acc.options()), db = at::empty({C}, acc.options());
+  kern::bn_dparams(acc.data_ptr<float>(), invstd.data_ptr<float>(), dw.data_ptr<float>(), db.data_ptr<float>(),
+                   static_cast<int>(C), stream_of(acc));
+  return {dw, db};
+}
+
 // BN training backward apply from an already masked gradient g and its
 // reduction acc = (Σg, Σg·(x - mean)): (dx, dweight, dbias).
 std::vector<at::Tensor> bn_bwd_apply_g(const at::Tensor& g, const at::Tensor& x, const at::Tensor& weight,
@@ -1885,6 +1941,11 @@ void bind(pybind11::module& m) {
         pybind11::arg("gy"), pybind11::arg("wt"), pybind11::arg("x"), pybind11::arg("gy2"), pybind11::arg("mean"),
         pybind11::arg("bits"), pybind11::arg("x2") = pybind11::none(), pybind11::arg("mean2") = pybind11::none());
   m.def("bn_bwd_apply_g", &bn_bwd_apply_g, "BN training backward apply from a masked gradient + its reduction");
+  m.def("conv3_bwd_fused", &conv3_bwd_fused,
+        "bottleneck conv3 backward with BN3's backward apply as its prologue -> (dy2, acc2, dz3)");
+  m.def("conv3_bwd_mode", [](int64_t M, int64_t w) { return kern::conv3_bwd_mode(M, static_cast<int>(w)); },
+        "0: conv3's backward of this shape stays unfused; 1: conv3_bwd_fused");
+  m.def("bn_dparams", &bn_dparams, "(dweight, dbias) of a training BN from its backward reduction");
   m.def("bn_bwd_apply2_g", &bn_bwd_apply2_g,
         "both BNs of relu(bn(x) + bn2(x2)) backward from the shared masked gradient in one pass");
   m.def("bn_act_bwd_apply", &bn_act_bwd_apply, "BN/ReLU training backward apply from a precomputed reduction");

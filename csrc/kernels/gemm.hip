@@ -37,6 +37,7 @@
 
 #include "gelu_math.h"
 #include "gemm_kernels.h"
+#include "kernels.h"
 #include "stem_kernels.h"
 
 namespace dcp {
@@ -2019,6 +2020,7 @@ void gemm_tune(const char* key, int value) {
   if (k == "reserve_cus") g_reserve_cus = value < 0 ? 0 : (value > 192 ? 192 : value);
   if (k.rfind("pp_", 0) == 0) gemm_pp_tune(key, value);
   if (k.rfind("bn_", 0) == 0) bn_tune(key, value);
+  if (k.rfind("c3bwd", 0) == 0) conv3_bwd_tune(key, value);
   wgrad_pp_tune(key, value);
 }
 int gemm_tune_get(const char* key) {
@@ -2036,6 +2038,7 @@ int gemm_tune_get(const char* key) {
   if (k == "reserve_cus") return g_reserve_cus;
   if (k.rfind("pp_", 0) == 0) return gemm_pp_tune_get(key);
   if (k.rfind("bn_", 0) == 0) return bn_tune_get(key);
+  if (k.rfind("c3bwd", 0) == 0) return conv3_bwd_tune_get(key);
   return wgrad_pp_tune_get(key);
 }
 

@@ -67,5 +67,23 @@ void copy_words(const int64_t* src, int64_t* dst, int64_t n, hipStream_t s);
 void comm_emulate(const void* src, void* scratch, int64_t bytes_buf, int64_t bytes_move, int channels, double us,
                   hipStream_t s);
 
+// conv3_bwd.hip: backward of a bottleneck's conv3 (1x1, w -> 4w channels, w =
+// 64 / 128) with BN3's backward apply as its prologue: dz3 = k1·(g − k2 −
+// (z3 − μ3)·k3) (bn_bwd_apply_kernel's expression and rounding; stored once
+// for the weight gradient), dy2 [M, w] = dz3 · W3 (wt = W3ᵀ bf16 [w][4w]) and
+// the BN2+ReLU backward reduction of gemm_nt's RED epilogue into stats
+// (zeroed fp32 [2w]) += (Σg2, Σg2·(x2 − μ2)). acc3 = (Σg, Σg·(z3 − μ3)) [2·4w].
+void conv3_bwd_bf16(const void* g, const void* z3, const void* wt, const void* x2, void* dz3, void* dy2, int64_t M,
+                    int w, const float* gamma3, const float* mean3, const float* invstd3, const float* acc3,
+                    const float* gamma2, const float* beta2, const float* mean2, const float* invstd2, float* stats,
+                    hipStream_t s);
+// 0 = this shape stays on the unfused path; 1 = conv3_bwd_bf16 (gemm_tune
+// "c3bwd" / "c3bwd64" / "c3bwd128"; "c3bwd_grid" caps the persistent grid)
+int conv3_bwd_mode(int64_t M, int w);
+bool conv3_bwd_tune(const char* key, int value);  // false: not one of its keys
+int conv3_bwd_tune_get(const char* key);          // -1: not one of its keys
+// dgamma = Σg(x−μ)·invstd, dbeta = Σg from acc = (Σg, Σg·(x − μ)) [2C]
+void bn_dparams(const float* acc, const float* invstd, float* dgamma, float* dbeta, int C, hipStream_t s);
+
 }  // namespace kern
 }  // namespace dcp

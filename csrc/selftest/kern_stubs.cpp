@@ -30,6 +30,15 @@ void mt_adadelta(TableView, int64_t, DType, float, float, float, float, bool, fl
 void mt_sumsq(TableView, int64_t, DType, float*, hipStream_t) { gpu_only("mt_sumsq"); }
 void mt_scale_by(TableView, int64_t, DType, const float*, hipStream_t) { gpu_only("mt_scale_by"); }
 void copy_words(const int64_t*, int64_t*, int64_t, hipStream_t) { gpu_only("copy_words"); }
+void conv3_bwd_bf16(const void*, const void*, const void*, const void*, void*, void*, int64_t, int, const float*,
+                    const float*, const float*, const float*, const float*, const float*, const float*, const float*,
+                    float*, hipStream_t) {
+  gpu_only("conv3_bwd_bf16");
+}
+int conv3_bwd_mode(int64_t, int) { return 0; }
+bool conv3_bwd_tune(const char*, int) { return false; }
+int conv3_bwd_tune_get(const char*) { return -1; }
+void bn_dparams(const float*, const float*, float*, float*, int, hipStream_t) { gpu_only("bn_dparams"); }
 
 }  // namespace kern
 }  // namespace dcp

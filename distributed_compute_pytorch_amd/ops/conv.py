@@ -120,6 +120,65 @@ class _Conv1x1Fn(torch.autograd.Function):
         return dx, dw, None
 
 
+# Deferred BN3 backward apply (csrc/kernels/conv3_bwd.hip): at an identity block
+# boundary `_BNResActConv1x1Fn.backward` does not materialise dz3; it returns
+# the masked gradient g in dz3's place and leaves (z3, gamma3, mean3, invstd3,
+# acc) here, keyed by g's storage address. The conv3 node that produced z3
+# (marked `_c3_defer` by `bn_res_act_conv1x1` at forward time) takes the entry
+# in its own backward and runs `_C.conv3_bwd_fused`, which forms dz3 on the way
+# into its data-gradient MFMAs. An entry lives from the boundary node's backward
+# to the conv3 node's, within one backward pass; the entry keeps g alive, so
+# the key cannot be reused meanwhile.
+_C3_DEFERRED: dict = {}
+
+
+def _c3_put(g: torch.Tensor, z3, gamma, mean, invstd, acc) -> None:
+    if _C3_DEFERRED:
+        _C3_DEFERRED.clear()
+        raise RuntimeError("conv3 backward fusion: a deferred BN3 gradient of an earlier node was never taken by its "
+                           "conv3 node (gemm_tune c3bwd=0 disables the fusion)")
+    _C3_DEFERRED[g.data_ptr()] = (g, z3, gamma, mean, invstd, acc)
+
+
+def _c3_take(ctx, gz: torch.Tensor):
+    """The deferred BN3 operands for the gradient ``gz`` of a conv3 node marked
+    at forward time, else None. A marked node whose gradient is not the one its
+    boundary node left (z3 had another consumer and autograd summed the
+    gradients, or the entry is stale) raises."""
+    if not getattr(ctx, "_c3_defer", False):
+        return None
+    e = _C3_DEFERRED.pop(gz.data_ptr(), None)
+    if e is None or e[0].shape != gz.shape or e[0].dtype != gz.dtype:
+        _C3_DEFERRED.clear()
+        raise RuntimeError("conv3 backward fusion: this node's z3 was handed to a fused block boundary, but the "
+                           "gradient it received is not that boundary's deferred one (z3 has another consumer?); "
+                           "gemm_tune c3bwd=0 disables the fusion")
+    return e[1:]
+
+
+def _c3_defer_ok(z3: torch.Tensor) -> bool:
+    """True (and the producing conv3 node is marked) when BN3's backward apply
+    over ``z3`` can be deferred into that node's backward."""
+    fn = z3.grad_fn
+    if fn is None or not torch.is_grad_enabled() or z3.dtype != torch.bfloat16 or z3.dim() != 4:
+        return False
+    if isinstance(fn, _BNReluConv1x1Fn._backward_cls):
+        if not _PRO_RED:
+            return False
+    elif isinstance(fn, _BNReluConvFn._backward_cls):
+        if fn.cfg[0] != 1 or fn.cfg[1] != 1:
+            return False
+    else:
+        return False
+    c = z3.shape[1]
+    if c % 4 or not z3.is_contiguous(memory_format=torch.channels_last):
+        return False
+    if _C.conv3_bwd_mode(z3.numel() // c, c // 4) <= 0:
+        return False
+    fn._c3_defer = True
+    return True
+
+
 # BN-prologue 1x1 conv (ResNet layer-1 conv3): BN backward reduce in the dgrad
 # epilogue (+0.6 %, profiles/r2_ab_pro_red.jsonl; False = separate reduce pass)
 _PRO_RED = True
@@ -145,10 +204,17 @@ class _BNReluConv1x1Fn(torch.autograd.Function):
         if gz is None:
             return (None,) * 11
         gz = _cl(gz)
+        d3 = _c3_take(ctx, gz)
+        if d3 is not None:
+            # gz is the masked gradient g of BN3's output: BN3's backward apply
+            # runs as the data-gradient kernel's prologue, which also stores dz3
+            da, acc, gz = _C.conv3_bwd_fused(gz, *d3, wt, x, gamma, beta, mean, invstd)
         dw = _C.conv1x1_wgrad(gz, x, scale, shift, True).view(ctx.wshape)
         if dw.dtype != ctx.wdtype:
             dw = dw.to(ctx.wdtype)
-        if _PRO_RED:
+        if d3 is not None:
+            dx, dgamma, dbeta = _C.bn_act_bwd_apply(da, x, gamma, beta, mean, invstd, acc)
+        elif _PRO_RED:
             # BN+ReLU backward reduction in the data-gradient GEMM's epilogue
             # (gemm.hip RED: mask recomputed from x), then the apply pass alone
             da, acc = _C.conv1x1_dgrad_bnred(gz, wt, x, gamma, beta, mean, invstd)
@@ -210,8 +276,9 @@ class _BNResActConv1x1Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z3, gamma, beta, residual, x2, gamma2, beta2, w_next, rm, rv, nbt, stats, rm2, rv2, nbt2,
-                stats2, momentum, eps, momentum2, eps2):
+                stats2, momentum, eps, momentum2, eps2, defer=False):
         ctx.set_materialize_grads(False)
+        ctx.defer = bool(defer) and x2 is None
         if x2 is not None:
             y, mean, invstd, bits, mean2, invstd2 = _C.bn_resbn_act_fwd(
                 z3, gamma, beta, rm, rv, nbt, stats, x2, gamma2, beta2, rm2, rv2, nbt2, stats2, float(momentum),
@@ -249,6 +316,12 @@ class _BNResActConv1x1Fn(torch.autograd.Function):
         if x2 is not None and _APPLY2:  # both BNs' apply passes share one read of g
             dz3, dgamma, dbeta, dx2, dgamma2, dbeta2 = _C.bn_bwd_apply2_g(g, z3, gamma, mean, invstd, acc, x2, gamma2,
                                                                           mean2, invstd2, acc2)
+        elif ctx.defer:
+            # identity block whose conv3 node forms dz3 itself (conv3_bwd.hip):
+            # g stands in for dz3, BN3's parameter gradients come from acc alone
+            _c3_put(g, z3, gamma, mean, invstd, acc)
+            dz3 = dres = g
+            dgamma, dbeta = _C.bn_dparams(acc, invstd)
         else:
             dz3, dgamma, dbeta = _C.bn_bwd_apply_g(g, z3, gamma, mean, invstd, acc)
             if x2 is not None:
@@ -258,7 +331,7 @@ class _BNResActConv1x1Fn(torch.autograd.Function):
         dw = dw.view(ctx.wshape)
         if dw.dtype != ctx.wdtype:
             dw = dw.to(ctx.wdtype)
-        return (dz3, dgamma, dbeta, dres, dx2, dgamma2, dbeta2, dw) + (None,) * 12
+        return (dz3, dgamma, dbeta, dres, dx2, dgamma2, dbeta2, dw) + (None,) * 13
 
 
 def bn_res_act_conv1x1(bn3, z3: torch.Tensor, s3: torch.Tensor, identity: Optional[torch.Tensor], w_next,
@@ -283,7 +356,7 @@ def bn_res_act_conv1x1(bn3, z3: torch.Tensor, s3: torch.Tensor, identity: Option
                                         bn_d.eps)
     return _BNResActConv1x1Fn.apply(z3, bn3.weight, bn3.bias, identity, None, None, None, w_next, bn3.running_mean,
                                     bn3.running_var, _nbt(bn3), s3, None, None, None, None, bn3.momentum, bn3.eps,
-                                    0.0, 0.0)
+                                    0.0, 0.0, not RES_PROLOGUE and _c3_defer_ok(z3))
 
 
 def res_conv_fuse_ok(bn3, z3: torch.Tensor, s3, next_conv) -> bool:
@@ -336,7 +409,11 @@ class _BNReluConvFn(torch.autograd.Function):
         x, y, gamma, beta, mean, invstd, w, wt = ctx.saved_tensors
         k, stride, pad, wshape, wdtype = ctx.cfg
         gz = _cl(gz)
-        if k == 1 and stride == 1:
+        d3 = _c3_take(ctx, gz)
+        if d3 is not None:  # marked nodes are 1x1 stride 1; gz is BN3's masked gradient g (conv3_bwd.hip)
+            dy, acc, gz = _C.conv3_bwd_fused(gz, *d3, wt, x, gamma, beta, mean, invstd)
+            dw = _C.conv1x1_wgrad(gz, y).view(wshape)
+        elif k == 1 and stride == 1:
             dw = _C.conv1x1_wgrad(gz, y).view(wshape)
             dy, acc = _C.conv1x1_dgrad_bnred(gz, wt, x, gamma, beta, mean, invstd)
         else:

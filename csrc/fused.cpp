@@ -1345,6 +1345,80 @@ std::vector<at::Tensor> bn_resbn_act_fwd(const at::Tensor& x, const at::Tensor& 
   return {y, mean, invstd, bits, mean2, invstd2};
 }
 
+// Block boundary forward with the next block's conv1 fed from the tile that
+// forms y (conv1_fwd.hip): y = relu(bn3(z3) + r), r = residual or bn_d(x2)
+// (training statistics from the producing GEMMs' epilogues, stats / stats2),
+// z1 = conv1x1(y, w) and its (Σz1, Σz1²). Returns (y, bits, z1, s1, mean,
+// invstd[, mean2, invstd2]) — what bn_act_fwd / bn_resbn_act_fwd followed by
+// conv1x1_fwd(stats) return, without the GEMM's re-read of y. Each BN's mean,
+// invstd, running statistics and num_batches_tracked come from bn_stats_coef's
+// finalize launch (the apply kernel's expressions: bit-identical).
+std::vector<at::Tensor> conv1_fwd_fused(const at::Tensor& z3, const at::Tensor& w, const at::Tensor& weight,
+                                        const at::Tensor& bias, const c10::optional<at::Tensor>& running_mean,
+                                        const c10::optional<at::Tensor>& running_var,
+                                        const c10::optional<at::Tensor>& nbt, const at::Tensor& stats, double momentum,
+                                        double eps, const c10::optional<at::Tensor>& residual,
+                                        const c10::optional<at::Tensor>& x2, const c10::optional<at::Tensor>& weight2,
+                                        const c10::optional<at::Tensor>& bias2,
+                                        const c10::optional<at::Tensor>& running_mean2,
+                                        const c10::optional<at::Tensor>& running_var2,
+                                        const c10::optional<at::Tensor>& nbt2,
+                                        const c10::optional<at::Tensor>& stats2, double momentum2, double eps2) {
+  check_gemm_act(z3, "conv1_fwd_fused");
+  c10::hip::HIPGuard guard(z3.device().index());
+  DK_CHECK(z3.dim() == 4, "conv1_fwd_fused: z3 must be a channels_last 4-D tensor");
+  const int64_t K = z3.size(1);
+  const int64_t M = z3.numel() / K;
+  DK_CHECK(w.scalar_type() == at::kBFloat16 && w.is_contiguous() && w.numel() % K == 0 && w.device() == z3.device(),
+            "conv1_fwd_fused: weight must be contiguous bf16 [N][K]");
+  const int64_t N = w.numel() / K;
+  DK_CHECK(kern::conv1_fwd_mode(M, static_cast<int>(K), static_cast<int>(N)) > 0, "conv1_fwd_fused: unsupported shape");
+  const bool rbn = x2.has_value() && x2->defined();
+  const bool ident = residual.has_value() && residual->defined();
+  DK_CHECK(rbn != ident, "conv1_fwd_fused: exactly one of residual and x2 is required");
+  const at::Tensor& res = rbn ? *x2 : *residual;
+  check_gemm_act(res, "conv1_fwd_fused");
+  DK_CHECK(res.sizes() == z3.sizes() && res.device() == z3.device(), "conv1_fwd_fused: residual / x2 must match z3");
+  auto f32c = [&](const at::Tensor& t, int64_t n) {
+    return t.scalar_type() == at::kFloat && t.numel() == n && t.is_contiguous() && t.device() == z3.device();
+  };
+  DK_CHECK(f32c(weight, K) && f32c(bias, K) && f32c(stats, 2 * K),
+            "conv1_fwd_fused: BN3 weight / bias fp32 [K], stats fp32 [2*K]");
+  auto nbt_ptr = [](const c10::optional<at::Tensor>& t) {
+    return t.has_value() && t->defined() ? t->data_ptr<int64_t>() : nullptr;
+  };
+  auto fopt = z3.options().dtype(at::kFloat);
+  auto s = stream_of(z3);
+  at::Tensor c3 = at::empty({4, K}, fopt);  // mean, invstd, scale, shift
+  kern::bn_stats_coef(kern::BN_BF16, z3.data_ptr(), M, static_cast<int>(K), weight.data_ptr<float>(),
+                      bias.data_ptr<float>(), fptr(running_mean), fptr(running_var), static_cast<float>(momentum),
+                      static_cast<float>(eps), c3[0].data_ptr<float>(), c3[1].data_ptr<float>(),
+                      c3[2].data_ptr<float>(), c3[3].data_ptr<float>(), stats.data_ptr<float>(), nbt_ptr(nbt), s, true);
+  at::Tensor cd;
+  if (rbn) {
+    DK_CHECK(weight2.has_value() && bias2.has_value() && stats2.has_value() && f32c(*weight2, K) &&
+                  f32c(*bias2, K) && f32c(*stats2, 2 * K),
+              "conv1_fwd_fused: downsample BN weight / bias fp32 [K], stats fp32 [2*K]");
+    cd = at::empty({4, K}, fopt);
+    kern::bn_stats_coef(kern::BN_BF16, res.data_ptr(), M, static_cast<int>(K), weight2->data_ptr<float>(),
+                        bias2->data_ptr<float>(), fptr(running_mean2), fptr(running_var2),
+                        static_cast<float>(momentum2), static_cast<float>(eps2), cd[0].data_ptr<float>(),
+                        cd[1].data_ptr<float>(), cd[2].data_ptr<float>(), cd[3].data_ptr<float>(),
+                        stats2->data_ptr<float>(), nbt_ptr(nbt2), s, true);
+  }
+  at::Tensor y = at::empty_like(z3, at::MemoryFormat::ChannelsLast);
+  at::Tensor bits = at::empty({M * K / 8}, z3.options().dtype(at::kByte));
+  at::Tensor z1 = at::empty({z3.size(0), N, z3.size(2), z3.size(3)},
+                            z3.options().memory_format(at::MemoryFormat::ChannelsLast));
+  at::Tensor s1 = zeroed_floats(2 * N, z3, s);
+  kern::conv1_fwd_bf16(z3.data_ptr(), res.data_ptr(), w.data_ptr(), y.data_ptr(), bits.data_ptr<uint8_t>(),
+                       z1.data_ptr(), M, static_cast<int>(K), static_cast<int>(N), c3[2].data_ptr<float>(),
+                       c3[3].data_ptr<float>(), rbn ? cd[2].data_ptr<float>() : nullptr,
+                       rbn ? cd[3].data_ptr<float>() : nullptr, s1.data_ptr<float>(), s);
+  if (rbn) return {y, bits, z1, s1, c3[0], c3[1], cd[0], cd[1]};
+  return {y, bits, z1, s1, c3[0], c3[1]};
+}
+
 // Backward of bn_resbn_act_fwd: (dx, dweight, dbias, dx2, dweight2, dbias2).
 std::vector<at::Tensor> bn_resbn_act_bwd(const at::Tensor& gy, const c10::optional<at::Tensor>& gy2_opt,
                                          const at::Tensor& x, const at::Tensor& weight, const at::Tensor& mean,
@@ -1946,6 +2020,20 @@ void bind(pybind11::module& m) {
   m.def("conv3_bwd_mode", [](int64_t M, int64_t w) { return kern::conv3_bwd_mode(M, static_cast<int>(w)); },
         "0: conv3's backward of this shape stays unfused; 1: conv3_bwd_fused");
   m.def("bn_dparams", &bn_dparams, "(dweight, dbias) of a training BN from its backward reduction");
+  m.def("conv1_fwd_fused", &conv1_fwd_fused,
+        "block boundary relu(bn3(z3) + residual-or-bn_d(x2)) with the next conv1 fed from the same tile -> "
+        "(y, bits, z1, sums1, mean, invstd[, mean2, invstd2])",
+        pybind11::arg("z3"), pybind11::arg("w"), pybind11::arg("weight"), pybind11::arg("bias"),
+        pybind11::arg("running_mean"), pybind11::arg("running_var"), pybind11::arg("num_batches_tracked"),
+        pybind11::arg("stats"), pybind11::arg("momentum"), pybind11::arg("eps"),
+        pybind11::arg("residual") = pybind11::none(), pybind11::arg("x2") = pybind11::none(),
+        pybind11::arg("weight2") = pybind11::none(), pybind11::arg("bias2") = pybind11::none(),
+        pybind11::arg("running_mean2") = pybind11::none(), pybind11::arg("running_var2") = pybind11::none(),
+        pybind11::arg("num_batches_tracked2") = pybind11::none(), pybind11::arg("stats2") = pybind11::none(),
+        pybind11::arg("momentum2") = 0.0, pybind11::arg("eps2") = 0.0);
+  m.def("conv1_fwd_mode",
+        [](int64_t M, int64_t K, int64_t N) { return kern::conv1_fwd_mode(M, static_cast<int>(K), static_cast<int>(N)); },
+        "0: the block boundary + conv1 forward of this shape stays unfused; 1: conv1_fwd_fused");
   m.def("bn_bwd_apply2_g", &bn_bwd_apply2_g,
         "both BNs of relu(bn(x) + bn2(x2)) backward from the shared masked gradient in one pass");
   m.def("bn_act_bwd_apply", &bn_act_bwd_apply, "BN/ReLU training backward apply from a precomputed reduction");

@@ -2021,6 +2021,7 @@ void gemm_tune(const char* key, int value) {
   if (k.rfind("pp_", 0) == 0) gemm_pp_tune(key, value);
   if (k.rfind("bn_", 0) == 0) bn_tune(key, value);
   if (k.rfind("c3bwd", 0) == 0) conv3_bwd_tune(key, value);
+  if (k.rfind("c1fwd", 0) == 0) conv1_fwd_tune(key, value);
   wgrad_pp_tune(key, value);
 }
 int gemm_tune_get(const char* key) {
@@ -2039,6 +2040,7 @@ int gemm_tune_get(const char* key) {
   if (k.rfind("pp_", 0) == 0) return gemm_pp_tune_get(key);
   if (k.rfind("bn_", 0) == 0) return bn_tune_get(key);
   if (k.rfind("c3bwd", 0) == 0) return conv3_bwd_tune_get(key);
+  if (k.rfind("c1fwd", 0) == 0) return conv1_fwd_tune_get(key);
   return wgrad_pp_tune_get(key);
 }
 

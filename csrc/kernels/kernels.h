@@ -85,5 +85,22 @@ int conv3_bwd_tune_get(const char* key);          // -1: not one of its keys
 // dgamma = Σg(x−μ)·invstd, dbeta = Σg from acc = (Σg, Σg·(x − μ)) [2C]
 void bn_dparams(const float* acc, const float* invstd, float* dgamma, float* dbeta, int C, hipStream_t s);
 
+// conv1_fwd.hip: forward of a block boundary with the next block's conv1 (1x1,
+// K -> N channels; ⟨K, N⟩ = ⟨256, 64⟩, ⟨512, 128⟩, ⟨256, 128⟩) fed from the
+// tile that forms y = relu(z3·scale + shift + r), r = res (rscale == nullptr)
+// or res·rscale + rshift (the downsample BN inline); bn_apply_kernel's
+// expression and rounding. Stores y [M, K], its mask bits (bit k of byte v =
+// y[8v + k] > 0), z1 [M, N] = y · wᵀ (w bf16 [N][K]) and gemm_nt's STATS sums
+// into stats (zeroed fp32 [2N]) += (Σz1, Σz1²) of the bf16-rounded z1.
+void conv1_fwd_bf16(const void* z3, const void* res, const void* w, void* y, uint8_t* bits, void* z1, int64_t M, int K,
+                    int N, const float* scale, const float* shift, const float* rscale, const float* rshift,
+                    float* stats, hipStream_t s);
+// 0 = this shape stays on the unfused path; 1 = conv1_fwd_bf16 (gemm_tune
+// "c1fwd" / "c1fwd64" / "c1fwd128" / "c1fwd256x128"; "c1fwd_grid" caps the
+// persistent grid)
+int conv1_fwd_mode(int64_t M, int K, int N);
+bool conv1_fwd_tune(const char* key, int value);  // false: not one of its keys
+int conv1_fwd_tune_get(const char* key);          // -1: not one of its keys
+
 }  // namespace kern
 }  // namespace dcp

@@ -39,6 +39,13 @@ int conv3_bwd_mode(int64_t, int) { return 0; }
 bool conv3_bwd_tune(const char*, int) { return false; }
 int conv3_bwd_tune_get(const char*) { return -1; }
 void bn_dparams(const float*, const float*, float*, float*, int, hipStream_t) { gpu_only("bn_dparams"); }
+void conv1_fwd_bf16(const void*, const void*, const void*, void*, uint8_t*, void*, int64_t, int, int, const float*,
+                    const float*, const float*, const float*, float*, hipStream_t) {
+  gpu_only("conv1_fwd_bf16");
+}
+int conv1_fwd_mode(int64_t, int, int) { return 0; }
+bool conv1_fwd_tune(const char*, int) { return false; }
+int conv1_fwd_tune_get(const char*) { return -1; }
 
 }  // namespace kern
 }  // namespace dcp

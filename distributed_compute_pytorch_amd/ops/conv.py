@@ -258,6 +258,33 @@ _APPLY2 = True
 RES_PROLOGUE = False
 
 
+def _c1_fused_ok(z3, gamma, beta, stats, res, gamma2, beta2, stats2, w_next) -> bool:
+    """True when ``_C.conv1_fwd_fused`` (csrc/kernels/conv1_fwd.hip) runs this
+    block boundary: conv1 of 256 -> 64, 512 -> 128 or 256 -> 128 channels
+    switched on in ``gemm_tune c1fwd*``, bf16 channels_last activations, fp32
+    BN parameters and epilogue sums for each BN. ``res``: the identity, or the
+    downsample BN's input when ``gamma2`` is given."""
+
+    def act(t):
+        return (t is not None and t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 4
+                and t.is_contiguous(memory_format=torch.channels_last))
+
+    def vec(t, n):
+        return t is not None and t.dtype == torch.float32 and t.numel() == n and t.is_contiguous()
+
+    if not act(z3) or res is None or res.shape != z3.shape or w_next.dim() != 4 or w_next.shape[2:] != (1, 1):
+        return False
+    k = z3.shape[1]
+    if w_next.shape[1] != k or not (vec(gamma, k) and vec(beta, k) and vec(stats, 2 * k)):
+        return False
+    if gamma2 is not None:
+        if not (act(res) and vec(gamma2, k) and vec(beta2, k) and vec(stats2, 2 * k)):
+            return False
+    elif res.dtype != torch.bfloat16 or res.dim() != 4:
+        return False
+    return _C.conv1_fwd_mode(z3.numel() // k, k, w_next.shape[0]) > 0
+
+
 class _BNResActConv1x1Fn(torch.autograd.Function):
     """Block boundary of a bottleneck chain, training mode:
     ``y = relu(bn3(z3) + r)`` with ``r`` the identity or ``bn_d(x2)`` (the
@@ -279,7 +306,20 @@ class _BNResActConv1x1Fn(torch.autograd.Function):
                 stats2, momentum, eps, momentum2, eps2, defer=False):
         ctx.set_materialize_grads(False)
         ctx.defer = bool(defer) and x2 is None
-        if x2 is not None:
+        if not RES_PROLOGUE and _c1_fused_ok(z3, gamma, beta, stats, residual if x2 is None else x2, gamma2, beta2,
+                                             stats2, w_next):
+            # y formed once per element in the kernel that multiplies it by W1
+            # (conv1_fwd.hip): no separate apply pass, no re-read of y
+            w, wt = _w2d(w_next)
+            mean2 = invstd2 = None
+            if x2 is not None:
+                y, bits, z1, s1, mean, invstd, mean2, invstd2 = _C.conv1_fwd_fused(
+                    z3, w, gamma, beta, rm, rv, nbt, stats, float(momentum), float(eps), None, x2, gamma2, beta2,
+                    rm2, rv2, nbt2, stats2, float(momentum2), float(eps2))
+            else:
+                y, bits, z1, s1, mean, invstd = _C.conv1_fwd_fused(z3, w, gamma, beta, rm, rv, nbt, stats,
+                                                                   float(momentum), float(eps), _cl(residual))
+        elif x2 is not None:
             y, mean, invstd, bits, mean2, invstd2 = _C.bn_resbn_act_fwd(
                 z3, gamma, beta, rm, rv, nbt, stats, x2, gamma2, beta2, rm2, rv2, nbt2, stats2, float(momentum),
                 float(eps), float(momentum2), float(eps2))

@@ -47,13 +47,12 @@
 #include <cmath>
 
 #include "attn_kernels.h"
+#include "bf16_vec.h"
 
 namespace dcp {
 namespace kern {
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -73,10 +72,6 @@ __device__ __forceinline__ f32x16 zero16() {
 #pragma unroll
   for (int r = 0; r < 16; ++r) z[r] = 0.f;
   return z;
-}
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-  const bf16x2 v = {static_cast<__bf16>(a), static_cast<__bf16>(b)};
-  return __builtin_bit_cast(uint32_t, v);
 }
 // an all-ones bf16 operand fragment (1.0 = 0x3F80)
 __device__ __forceinline__ bf16x8 ones_frag() {

@@ -28,16 +28,12 @@
 
 #include <cstring>
 
+#include "bf16_vec.h"
 #include "kernels.h"
 
 namespace dcp {
 namespace kern {
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kBM = 32;  // rows per tile: z3 + residual of one tile = 32 KB (K = 256) / 64 KB (K = 512) in flight per workgroup
 
@@ -48,23 +44,6 @@ int g_mode128 = 1;      // ⟨512, 128⟩
 int g_mode256x128 = 1;  // ⟨256, 128⟩
 // gemm_tune "c1fwd_grid": > 0 caps the persistent grid (tests: several tiles per workgroup)
 int g_grid = 0;
-
-__device__ __forceinline__ float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-// two fp32 → packed bf16 (RNE) in one v_cvt_pk_bf16_f32
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-  const bf16x2 v = {static_cast<__bf16>(a), static_cast<__bf16>(b)};
-  return __builtin_bit_cast(uint32_t, v);
-}
-// streaming 16-B accesses (batchnorm.hip: nothing caches these tensors between passes)
-__device__ __forceinline__ uint4 ld16_nt(const uint16_t* p) {
-  const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ void st16_nt(uint16_t* p, uint4 v) {
-  const u32x4 w = {v.x, v.y, v.z, v.w};
-  __builtin_nontemporal_store(w, reinterpret_cast<u32x4*>(p));
-}
 
 struct C1Args {
   const uint16_t* z3;   // [M, K] BN3's input
@@ -98,9 +77,7 @@ __global__ void __launch_bounds__(4 * N) conv1_fwd_kernel(const C1Args a) {
   const int64_t M = a.M;
 
   // workgroup id → tile id through gemm_nt's bijective XCD remap
-  const int P = gridDim.x, wid = blockIdx.x;
-  const int xcd = wid & 7, q8 = P >> 3, r8 = P & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (wid >> 3);
+  const int P = gridDim.x, wg = xcd_remap(blockIdx.x, P);
 
   // folded coefficients of this thread's 8 channels
   float sc[8], sf[8], rsc[RBN ? 8 : 1], rsf[RBN ? 8 : 1];

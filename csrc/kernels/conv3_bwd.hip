@@ -27,16 +27,12 @@
 
 #include <cstring>
 
+#include "bf16_vec.h"
 #include "kernels.h"
 
 namespace dcp {
 namespace kern {
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kBM = 32;  // rows per tile: g + z3 of one tile = 32 KB (w = 64) / 64 KB (w = 128) in flight per workgroup
 
@@ -46,23 +42,6 @@ int g_mode64 = 1;
 int g_mode128 = 1;
 // gemm_tune "c3bwd_grid": > 0 caps the persistent grid (tests: several tiles per workgroup)
 int g_grid = 0;
-
-__device__ __forceinline__ float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-// two fp32 → packed bf16 (RNE) in one v_cvt_pk_bf16_f32
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-  const bf16x2 v = {static_cast<__bf16>(a), static_cast<__bf16>(b)};
-  return __builtin_bit_cast(uint32_t, v);
-}
-// streaming 16-B accesses (batchnorm.hip: nothing caches these tensors between passes)
-__device__ __forceinline__ uint4 ld16_nt(const uint16_t* p) {
-  const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ void st16_nt(uint16_t* p, uint4 v) {
-  const u32x4 w = {v.x, v.y, v.z, v.w};
-  __builtin_nontemporal_store(w, reinterpret_cast<u32x4*>(p));
-}
 
 struct C3Args {
   const uint16_t* g;    // [M, 4w] masked gradient of BN3's output
@@ -101,9 +80,7 @@ __global__ void __launch_bounds__(4 * W) conv3_bwd_kernel(const C3Args a) {
   const int64_t M = a.M;
 
   // workgroup id → tile id through gemm_nt's bijective XCD remap
-  const int P = gridDim.x, wid = blockIdx.x;
-  const int xcd = wid & 7, q8 = P >> 3, r8 = P & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (wid >> 3);
+  const int P = gridDim.x, wg = xcd_remap(blockIdx.x, P);
 
   // BN3 backward coefficients of this thread's 8 channels (bn_bwd_apply_kernel's expressions)
   float k1[8], k2[8], k3[8], mu[8];

@@ -35,6 +35,7 @@
 #include <cstdlib>
 #include <string>
 
+#include "bf16_vec.h"
 #include "gelu_math.h"
 #include "gemm_kernels.h"
 #include "kernels.h"
@@ -44,10 +45,8 @@ namespace dcp {
 namespace kern {
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 constexpr int kT = 256;
@@ -57,15 +56,6 @@ int g_wg_slots = 512;
 int g_wg_cap = 0;
 constexpr int kBK = 32;  // k per stage
 constexpr int kNS = 4;   // LDS ring stages
-
-__device__ __forceinline__ float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-// two fp32 → packed bf16 (RNE) in one v_cvt_pk_bf16_f32
-__device__ __forceinline__ uint32_t pack2(float a, float b) {
-  const bf16x2 v = {static_cast<__bf16>(a), static_cast<__bf16>(b)};
-  return __builtin_bit_cast(uint32_t, v);
-}
 
 __device__ __forceinline__ void glds16(const void* src, char* lds_dst) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
@@ -414,8 +404,7 @@ __global__ void __launch_bounds__((nt_threads<BM, BN>()), (nt_threads<BM, BN>() 
   // == 0 keeps the block's n-tile — and its STATS channels — fixed).
   int P = static_cast<int>(gridDim.x);
   const int wid = static_cast<int>(blockIdx.x);
-  const int xcd = wid & 7, q8 = P >> 3, r8 = P & 7;
-  int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (wid >> 3);
+  int wg = xcd_remap(wid, P);
   int64_t ldb = K;
   if constexpr (PAR) {
     if (mg.n > 0) {  // multi-class launch: this workgroup's class, one tile
@@ -1097,8 +1086,7 @@ __global__ void __launch_bounds__(kT, 2) gemm_wgrad_kernel(const uint16_t* __res
   {
     const int nwg = static_cast<int>(gridDim.x), wid = static_cast<int>(blockIdx.x);
     if (order == 1) {
-      const int xcd = wid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-      const int lin = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (wid >> 3);
+      const int lin = xcd_remap(wid, nwg);
       bz = lin % ntaps;
       const int rest = lin / ntaps;
       bx = rest % ntiles;

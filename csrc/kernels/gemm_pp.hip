@@ -52,16 +52,13 @@
 #include <string>
 #include <type_traits>
 
+#include "bf16_vec.h"
 #include "gelu_math.h"
 #include "gemm_kernels.h"
 
 namespace dcp {
 namespace kern {
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kPT = 512;                   // threads
 constexpr int kHT = 16384;                 // half-tile bytes: 128 rows x 128 B
@@ -172,8 +169,7 @@ __global__ void __launch_bounds__(kPT, 1)
   // fastest, then K-splits (one XCD's workgroups share a K range)
   const int P = static_cast<int>(gridDim.x);
   const int wid = static_cast<int>(blockIdx.x);
-  const int xcd = wid & 7, q8 = P >> 3, r8 = P & 7;
-  const int vl = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (wid >> 3);
+  const int vl = xcd_remap(wid, P);
   const int ntl = static_cast<int>((M + 255) >> 8) * tiles_n;
   const int v = SK ? vl % ntl : vl;
   const int ks = SK ? vl / ntl : 0;
@@ -514,8 +510,7 @@ __global__ void __launch_bounds__(kPT, 1)
   // consecutive tile ids (the N-tiles of an M-tile share A in that XCD's L2)
   const int P = static_cast<int>(gridDim.x);
   const int wid = static_cast<int>(blockIdx.x);
-  const int xcd = wid & 7, q8 = P >> 3, r8 = P & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (wid >> 3);
+  const int wg = xcd_remap(wid, P);
   const int tiles = tiles_m * tiles_n;
   const int KT = K >> 6;
   const int G = ((tiles - wg + P - 1) / P) * KT;  // K-tiles this workgroup streams

@@ -31,16 +31,13 @@
 #include <cstdint>
 #include <stdexcept>
 
+#include "bf16_vec.h"
 #include "gelu_math.h"
 #include "gemm_kernels.h"
 
 namespace dcp {
 namespace kern {
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kPT = 512;
 constexpr int kBM = 128, kBN = 192;
@@ -105,8 +102,7 @@ __global__ void __launch_bounds__(kPT, 1)
   // (the N-tiles of an M-tile share A through that XCD's L2)
   const int P = static_cast<int>(gridDim.x);
   const int wid = static_cast<int>(blockIdx.x);
-  const int xcd = wid & 7, q8 = P >> 3, r8 = P & 7;
-  const int v = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (wid >> 3);
+  const int v = xcd_remap(wid, P);
   const int64_t m0 = static_cast<int64_t>(v / tiles_n) * kBM;
   const int n0 = (v % tiles_n) * kBN;
   const int KT = K >> 6;

@@ -41,16 +41,15 @@
 #include <stdexcept>
 #include <string>
 
+#include "bf16_vec.h"
 #include "gemm_kernels.h"
 
 namespace dcp {
 namespace kern {
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4 wp_lds_s16x4;
 
 constexpr int kPT = 512;                // threads
@@ -148,6 +147,7 @@ __global__ void __launch_bounds__(kPT, 1)
     const int P = direct ? fw : static_cast<int>(gridDim.x) - fw;
     const int wid = static_cast<int>(blockIdx.x) - (direct ? 0 : fw);
     const int nt = direct ? nfull : ntiles - nfull;
+    // xcd_remap() written out: this site is deliberately left unconverted (NOTES §37)
     const int xcd = wid & 7, q8 = P >> 3, r8 = P & 7;
     const int lin = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (wid >> 3);
     bz = lin % ntaps;

@@ -1205,7 +1205,16 @@ kern::AttnParams attn_params(const at::Tensor& q, int64_t heads, bool causal, do
   p.seed = static_cast<uint64_t>(seed);
   p.mask = nullptr;
   p.kmask = nullptr;
+  p.seed_off = nullptr;
   return p;
+}
+// the device-resident seed offset of the dropout forward (AttnParams::seed_off), or none
+const uint64_t* attn_seed_off(const c10::optional<at::Tensor>& off, const at::Tensor& q, const char* what) {
+  if (!off.has_value() || !off->defined()) return nullptr;
+  DK_CHECK(off->is_cuda() && off->device() == q.device() && off->scalar_type() == at::kLong &&
+               off->is_contiguous() && off->numel() == 1,
+           what, ": seed_offset must be a contiguous int64 tensor with one element on q's device");
+  return reinterpret_cast<const uint64_t*>(off->data_ptr<int64_t>());
 }
 // the packed key mask of attn_pack_key_mask for this (B, T), or none
 const uint64_t* attn_kmask(const c10::optional<at::Tensor>& km, const at::Tensor& q, const kern::AttnParams& p,
@@ -1245,15 +1254,21 @@ at::Tensor attn_pack_key_mask(const at::Tensor& mask) {
 }
 
 // o [B, T, H*64] (contiguous), lse [B*H, T] fp32 (log2 domain), keep bits
-// (int32 [attn_mask_words], T²/8 bytes per head; empty without dropout)
+// (int32 [attn_mask_words], T²/8 bytes per head; empty without dropout).
+// seed_offset: the dropout hash runs on seed + offset * 0x9E3779B97F4A7C15,
+// the offset read on the device when the kernel runs (every replay of a
+// captured call reads it anew); the keep bits carry the decisions to the
+// backward, which takes no offset
 std::vector<at::Tensor> flash_attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, int64_t heads,
                                        bool causal, double p_drop, int64_t seed, bool keep_bits,
-                                       const c10::optional<at::Tensor>& key_mask) {
+                                       const c10::optional<at::Tensor>& key_mask,
+                                       const c10::optional<at::Tensor>& seed_offset) {
   same_shape(q, k, "flash_attn_fwd");
   same_shape(q, v, "flash_attn_fwd");
   c10::hip::HIPGuard guard(q.device().index());
   kern::AttnParams p = attn_params(q, heads, causal, p_drop, seed);
   p.kmask = attn_kmask(key_mask, q, p, "flash_attn_fwd");
+  p.seed_off = attn_seed_off(seed_offset, q, "flash_attn_fwd");
   at::Tensor o = at::empty(q.sizes(), q.options().memory_format(at::MemoryFormat::Contiguous));
   at::Tensor lse = at::empty({q.size(0) * heads, q.size(1)}, q.options().dtype(at::kFloat));
   // the keep bits only when a backward will read them (T²/8 bytes per head)
@@ -1996,7 +2011,8 @@ void bind(pybind11::module& m) {
   m.def("flash_attn_fwd", &flash_attn_fwd, "MFMA flash attention forward (head dim 64)", pybind11::arg("q"),
         pybind11::arg("k"), pybind11::arg("v"), pybind11::arg("heads"), pybind11::arg("causal"),
         pybind11::arg("p_drop"), pybind11::arg("seed"), pybind11::arg("keep_bits") = true,
-        pybind11::arg("key_mask") = pybind11::none());
+        pybind11::arg("key_mask") = pybind11::none(), pybind11::kw_only(),
+        pybind11::arg("seed_offset") = pybind11::none());
   m.def("flash_attn_bwd", &flash_attn_bwd, "MFMA flash attention backward into dq/dk/dv", pybind11::arg("dout"),
         pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"), pybind11::arg("o"), pybind11::arg("lse"),
         pybind11::arg("keep"), pybind11::arg("heads"), pybind11::arg("causal"), pybind11::arg("p_drop"),

@@ -331,7 +331,13 @@ __global__ void __launch_bounds__(kT) attn_fwd_kernel(AttnParams P, AttnTensor q
   const float c = P.scale * kLog2e;
   const uint32_t thr = drop_thr(P.p_drop);
   const uint32_t tb = (thr & 0x7fu) * 0x01010101u, ta = thr < 128u ? ~0u : 0u;
-  const uint32_t kbh = drop_key(static_cast<uint32_t>(P.seed), static_cast<uint32_t>(P.seed >> 32), bh);
+  // effective seed: the host seed plus the device-resident offset (a captured
+  // step's dropout counter: the host seed is frozen into the graph, the
+  // offset differs on every replay) times the 64-bit golden-ratio constant.
+  // One wave-uniform 8-byte load per workgroup; null or 0: the seed itself
+  uint64_t seed = P.seed;
+  if (DROP && P.seed_off != nullptr) seed += *P.seed_off * 0x9E3779B97F4A7C15ull;
+  const uint32_t kbh = drop_key(static_cast<uint32_t>(seed), static_cast<uint32_t>(seed >> 32), bh);
 
   float m = -INFINITY, l = 0.f;
   f32x16 oacc[2] = {zero16(), zero16()};
@@ -500,7 +506,7 @@ __global__ void __launch_bounds__(kT) attn_fwd_kernel(AttnParams P, AttnTensor q
 // and O (4 more 16-B loads per lane, behind the first K/V stage), and stored
 // for the dK/dV kernel, which runs after this one (no separate δ pass).
 template <bool CAUSAL, bool DROP, bool KMASK>
-__global__ void __launch_bounds__(kT) attn_bwd_dq_kernel(AttnParams P, AttnTensor q, AttnTensor k, AttnTensor v,
+__global__ void __launch_bounds__(kT) attn_bwd_dq_kernel(AttnCoreParams P, AttnTensor q, AttnTensor k, AttnTensor v,
                                                          AttnTensor dout, AttnTensor o, const float* __restrict__ lse,
                                                          float* __restrict__ delta, AttnOut dq) {
   __shared__ __attribute__((aligned(16))) char lds[2 * 2 * kTile];
@@ -656,7 +662,7 @@ __global__ void __launch_bounds__(kT) attn_bwd_dq_kernel(AttnParams P, AttnTenso
 // dVᵀ += dOᵀ·(P∘keep/(1-p)), dKᵀ += Qᵀ·dS. Q / dO tiles (+ LSE, δ) stream
 // through LDS; each wave keeps its 32 keys' dKᵀ, dVᵀ in registers.
 template <bool CAUSAL, bool DROP, bool KMASK>
-__global__ void __launch_bounds__(kT) attn_bwd_dkv_kernel(AttnParams P, AttnTensor q, AttnTensor k, AttnTensor v,
+__global__ void __launch_bounds__(kT) attn_bwd_dkv_kernel(AttnCoreParams P, AttnTensor q, AttnTensor k, AttnTensor v,
                                                           AttnTensor dout, const float* __restrict__ lse,
                                                           const float* __restrict__ delta, AttnOut dk, AttnOut dv) {
   // Q | dO | lse | delta | keep words [key block kb0/64 + {0,1}][hh][64 queries]
@@ -914,10 +920,11 @@ void attn_bwd(const AttnParams& p, AttnTensor q, AttnTensor k, AttnTensor v, Att
   const dim3 grid(p.B * p.H, (p.T + 127) / 128);
   const bool drop = p.p_drop > 0.f;
   const bool km = p.kmask != nullptr;
+  const AttnCoreParams& c = p;  // the backward kernels' part: without the forward-only seed offset
 #define DK_AB(C, D, M)                                                                                             \
   do {                                                                                                              \
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<C, D, M>), grid, dim3(kT), 0, s, p, q, k, v, dout, o, lse, delta, dq);   \
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<C, D, M>), grid, dim3(kT), 0, s, p, q, k, v, dout, lse, delta, dk, dv); \
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<C, D, M>), grid, dim3(kT), 0, s, c, q, k, v, dout, o, lse, delta, dq);   \
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<C, D, M>), grid, dim3(kT), 0, s, c, q, k, v, dout, lse, delta, dk, dv); \
   } while (0)
 #define DK_ABM(C, D)         \
   do {                       \

@@ -22,7 +22,10 @@ struct AttnOut {
   int64_t sb, st;
 };
 
-struct AttnParams {
+// What every kernel reads; the backward kernels take exactly this by value, so
+// a field only the forward reads (AttnParams) leaves their kernel arguments,
+// and with them their instruction streams, as they are.
+struct AttnCoreParams {
   int B, H, T;
   float scale;       // softmax scale (1/sqrt(64))
   bool causal;
@@ -41,6 +44,16 @@ struct AttnParams {
   // the forward (unless null: no backward will run), read by the backward;
   // unused when p_drop == 0
   uint32_t* mask;
+};
+
+// The forward's parameters (attn_bwd reads the AttnCoreParams part only).
+struct AttnParams : AttnCoreParams {
+  // device-resident seed offset (one uint64), read by the dropout forward
+  // only: its hash runs on seed + *seed_off * 0x9E3779B97F4A7C15 (mod 2^64).
+  // Null: no offset. A captured step passes the dropout counter here, so
+  // every replay draws new keep decisions although `seed` is frozen into the
+  // graph. (Behind mask: the fields above keep their kernel-argument offsets)
+  const uint64_t* seed_off;
 };
 
 // uint64 words of the packed key mask

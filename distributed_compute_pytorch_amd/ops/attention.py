@@ -26,13 +26,29 @@ nor compute the trailing ones. Zero-row rule: a query that sees no key at all
 row of exactly 0 and a dQ row of exactly 0 and adds nothing to dK / dV — where
 a softmax over an empty set would give NaN. ``key_mask=None`` runs the kernels
 that carry no mask code.
+
+Dropout under graph capture. Every call draws a host seed (``seed=None``) and
+passes it to the kernels by value, so a captured call has its seed frozen into
+the graph. The forward therefore takes an optional device-resident *seed
+offset* (``seed_offset=``, an int64 tensor with one element) and hashes with
+``seed + offset * 0x9E3779B97F4A7C15 (mod 2^64)``, the offset read when the
+kernel runs. A call with ``seed=None`` and ``dropout_p > 0`` on a capturing
+stream takes the dropout counter of ``ops/dropout.py`` as its offset, the way
+the Philox ops do (a snapshot + advance per call, or the counter itself inside
+``batched_offsets``, whose step-end add then advances it): every replay draws
+a fresh keep mask, and the calls of one replay stay independent through their
+own host seeds. The backward reads the stored keep bits and needs no offset.
+Eager calls skip the counter (a GPU call with dropout creates it, so that an
+attention-only warm-up permits capture).
 """
 from __future__ import annotations
 
 import torch
 
 from .._ext import C as _C
+from . import dropout as _dropout
 
+_GOLDEN64 = 0x9E3779B97F4A7C15
 
 def _seed() -> int:
     # from torch's CPU generator: torch.manual_seed makes runs reproducible
@@ -54,10 +70,40 @@ def _km_args(km):
     return () if km is None else (km,)
 
 
+def _off_kwargs(off):
+    return {} if off is None else {"seed_offset": off}
+
+
+def _check_seed_offset(off):
+    if off is None:
+        return None
+    if not isinstance(off, torch.Tensor):
+        raise TypeError(f"seed_offset: an int64 tensor with one element required, got {type(off).__name__}")
+    if off.dtype != torch.int64:
+        raise TypeError(f"seed_offset: an int64 tensor required, got {off.dtype}")
+    if off.numel() != 1:
+        raise ValueError(f"seed_offset: a tensor with one element required, got shape {tuple(off.shape)}")
+    return off
+
+
+def _seed_and_offset(x, dropout_p, seed, seed_offset):
+    """(host seed, device offset or None) of one call on ``x``'s device."""
+    off = _check_seed_offset(seed_offset)
+    if seed is not None:
+        return int(seed), off
+    if off is None and dropout_p > 0.0 and x.is_cuda:
+        if _dropout._capturing():
+            off = _dropout.take_counter(x.device)
+        else:
+            _dropout._ensure_counter(x.device)
+    return _seed(), off
+
+
 class _FlashAttnFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, heads, causal, p_drop, seed, keep_bits, km):
-        o, lse, keep = _C.flash_attn_fwd(q, k, v, heads, causal, p_drop, seed, keep_bits, *_km_args(km))
+    def forward(ctx, q, k, v, heads, causal, p_drop, seed, keep_bits, km, off):
+        o, lse, keep = _C.flash_attn_fwd(q, k, v, heads, causal, p_drop, seed, keep_bits, *_km_args(km),
+                                         **_off_kwargs(off))
         ctx.save_for_backward(q, k, v, o, lse, keep, km)
         ctx.cfg = (heads, causal, p_drop, seed)
         return o
@@ -72,15 +118,16 @@ class _FlashAttnFn(torch.autograd.Function):
         dq, dk, dv = torch.empty_like(q, memory_format=torch.contiguous_format), torch.empty_like(
             k, memory_format=torch.contiguous_format), torch.empty_like(v, memory_format=torch.contiguous_format)
         _C.flash_attn_bwd(do, q, k, v, o, lse, keep, heads, causal, p_drop, seed, dq, dk, dv, *_km_args(km))
-        return dq, dk, dv, None, None, None, None, None, None
+        return dq, dk, dv, None, None, None, None, None, None, None
 
 
 class _FlashAttnQKVFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, heads, causal, p_drop, seed, keep_bits, km):
+    def forward(ctx, qkv, heads, causal, p_drop, seed, keep_bits, km, off):
         C = qkv.shape[2] // 3
         q, k, v = qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:]
-        o, lse, keep = _C.flash_attn_fwd(q, k, v, heads, causal, p_drop, seed, keep_bits, *_km_args(km))
+        o, lse, keep = _C.flash_attn_fwd(q, k, v, heads, causal, p_drop, seed, keep_bits, *_km_args(km),
+                                         **_off_kwargs(off))
         ctx.save_for_backward(qkv, o, lse, keep, km)
         ctx.cfg = (heads, causal, p_drop, seed)
         return o
@@ -97,7 +144,7 @@ class _FlashAttnQKVFn(torch.autograd.Function):
         q, k, v = qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:]
         dq, dk, dv = dqkv[..., :C], dqkv[..., C:2 * C], dqkv[..., 2 * C:]
         _C.flash_attn_bwd(do, q, k, v, o, lse, keep, heads, causal, p_drop, seed, dq, dk, dv, *_km_args(km))
-        return dqkv, None, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None, None
 
 
 def pack_key_mask(mask: torch.Tensor) -> torch.Tensor:
@@ -143,7 +190,8 @@ def _packed_key_mask(key_mask, B: int, T: int):
 
 
 def flash_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, causal: bool = False,
-               dropout_p: float = 0.0, seed: int = None, key_mask: torch.Tensor = None) -> torch.Tensor:
+               dropout_p: float = 0.0, seed: int = None, key_mask: torch.Tensor = None,
+               seed_offset: torch.Tensor = None) -> torch.Tensor:
     """softmax(q kᵀ / 8 [+ causal mask] [+ key mask]) → dropout(p) → · v, per head of 64.
 
     ``key_mask``: a [B, T] bool key-padding mask (True = the key takes part;
@@ -156,19 +204,30 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, ca
     work: changing the mask's contents in place between replays changes the
     result accordingly (forward and backward). Given a tensor packed outside
     the capture, replays read those packed bits: later changes to the bool
-    mask they were made from are not seen."""
+    mask they were made from are not seen.
+
+    Dropout: the keep decisions are a hash of ``seed`` (drawn from torch's CPU
+    generator when None) plus ``seed_offset`` (an int64 tensor with one
+    element on q's device, read by the kernel when it runs) times
+    0x9E3779B97F4A7C15 (module docstring; :func:`dropout_keep_mask` is the
+    oracle). With ``seed=None`` and no ``seed_offset``, a call on a capturing
+    stream takes the dropout counter as its offset, so every replay draws a
+    fresh mask. An explicit ``seed=`` without ``seed_offset=`` keeps its plain
+    meaning: the mask is that seed's, frozen under capture, the same on every
+    replay."""
+    host_seed, off = _seed_and_offset(q, float(dropout_p), seed, seed_offset)
     km = _packed_key_mask(key_mask, q.shape[0], q.shape[1])
-    return _FlashAttnFn.apply(q, k, v, heads, causal, float(dropout_p), _seed() if seed is None else int(seed),
-                              _backward_will_run(q, k, v), km)
+    return _FlashAttnFn.apply(q, k, v, heads, causal, float(dropout_p), host_seed, _backward_will_run(q, k, v), km,
+                              off)
 
 
 def flash_attn_qkv(qkv: torch.Tensor, heads: int, causal: bool = False, dropout_p: float = 0.0,
-                   seed: int = None, key_mask: torch.Tensor = None) -> torch.Tensor:
+                   seed: int = None, key_mask: torch.Tensor = None, seed_offset: torch.Tensor = None) -> torch.Tensor:
     """:func:`flash_attn` on the three slices of a packed [B, T, 3*H*64]
-    projection (``key_mask`` as there)."""
+    projection (``key_mask``, ``seed`` and ``seed_offset`` as there)."""
+    host_seed, off = _seed_and_offset(qkv, float(dropout_p), seed, seed_offset)
     km = _packed_key_mask(key_mask, qkv.shape[0], qkv.shape[1])
-    return _FlashAttnQKVFn.apply(qkv, heads, causal, float(dropout_p), _seed() if seed is None else int(seed),
-                                 _backward_will_run(qkv), km)
+    return _FlashAttnQKVFn.apply(qkv, heads, causal, float(dropout_p), host_seed, _backward_will_run(qkv), km, off)
 
 
 def _backward_will_run(*ts) -> bool:
@@ -185,28 +244,37 @@ def dropout_p_effective(p: float) -> float:
 
 
 def flash_attn_keep_bits(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, causal: bool,
-                         dropout_p: float, seed: int) -> torch.Tensor:
+                         dropout_p: float, seed: int, seed_offset: torch.Tensor = None) -> torch.Tensor:
     """The dropout keep decisions the forward stored for the backward, decoded
-    to a bool [B, H, T, T] (test hook). Causal: entries above the diagonal are
-    not stored (never read) and come back as False."""
+    to a bool [B, H, T, T] (test hook; ``seed_offset`` as in
+    :func:`flash_attn`). Causal: entries above the diagonal are not stored
+    (never read) and come back as False."""
     B, T = q.shape[0], q.shape[1]
-    _, _, words = _C.flash_attn_fwd(q, k, v, heads, causal, float(dropout_p), int(seed))
+    off = _check_seed_offset(seed_offset)
+    _, _, words = _C.flash_attn_fwd(q, k, v, heads, causal, float(dropout_p), int(seed), **_off_kwargs(off))
+    return decode_keep_bits(words, B, heads, T, causal)
+
+
+def decode_keep_bits(words: torch.Tensor, B: int, heads: int, T: int, causal: bool) -> torch.Tensor:
+    """The keep words of ``_C.flash_attn_fwd`` as a bool [B, H, T, T]."""
     nblk = T // 64
     w = words.view(B * heads, nblk, 2, T).to(torch.int64) & 0xFFFFFFFF
-    kk = torch.arange(64, device=q.device)
+    kk = torch.arange(64, device=words.device)
     # key 32kh + 8g + 4hh + e of a 64-key block: word half hh, bit 8e + 4kh + g
     hh, bit = (kk >> 2) & 1, 8 * (kk & 3) + 4 * ((kk >> 5) & 1) + ((kk >> 3) & 3)
     sel = w[:, :, hh, :]                                   # [BH, nblk, 64 keys, T queries]
     bits = (sel >> bit[None, None, :, None]) & 1
     m = bits.permute(0, 3, 1, 2).reshape(B, heads, T, T).bool()
     if causal:
-        m &= torch.ones(T, T, dtype=torch.bool, device=q.device).tril()
+        m &= torch.ones(T, T, dtype=torch.bool, device=words.device).tril()
     return m
 
 
-def dropout_keep_mask(B: int, H: int, T: int, p: float, seed: int, device=None) -> torch.Tensor:
+def dropout_keep_mask(B: int, H: int, T: int, p: float, seed: int, device=None, offset: int = 0) -> torch.Tensor:
     """The kernels' dropout keep-mask [B, H, T, T] rebuilt with integer torch
-    ops (test oracle). Per (query q, 64-key block k, lane half hh):
+    ops (test oracle). ``offset``: the value of the forward's ``seed_offset``
+    tensor; the hash runs on seed + offset·0x9E3779B97F4A7C15 (mod 2^64).
+    Per (query q, 64-key block k, lane half hh):
     x0 = fmix32(((q << 8) | (k << 1) | hh) ^ kbh), kbh = fmix32(s0 ^
     fmix32(bh·0x9E3779B1 + s1)) (murmur3 finaliser); word j (j < 8) is
     xorshift32 (13/17/5) applied j times to x0, XOR j·0x9E3779B9; key
@@ -232,6 +300,7 @@ def dropout_keep_mask(B: int, H: int, T: int, p: float, seed: int, device=None) 
         return x ^ ((x << 5) & M)
 
     nblk = T // 64
+    seed = (int(seed) + int(offset) * _GOLDEN64) & 0xFFFFFFFFFFFFFFFF
     s0, s1 = seed & M, (seed >> 32) & M
     i64 = dict(device=dev, dtype=torch.int64)
     bh = torch.arange(B * H, **i64)[:, None, None, None]

@@ -7,7 +7,9 @@ the reference seeds every rank identically). Inside a HIP-graph capture the
 drawn seed is frozen into the graph, so the call also snapshots and advances
 a per-device Philox counter tensor (two tiny captured kernels): every replay
 reads a new counter value and draws fresh masks. Eager calls skip the counter.
-``dropout_add(x, residual, p)`` fuses the transformer residual add.
+The attention dropout of ``ops/attention.py`` (its own hash, not Philox) takes
+the same counter under capture (:func:`take_counter`) as its device-resident
+seed offset. ``dropout_add(x, residual, p)`` fuses the transformer residual add.
 """
 from __future__ import annotations
 
@@ -60,16 +62,26 @@ def _take_offset(device, n):
     if device.type != "cuda" or not _capturing():
         _ensure_counter(device)
         return seed, None
+    return seed, take_counter(device, (n + 3) // 4)
+
+
+def take_counter(device, n: int = 1) -> torch.Tensor:
+    """The device counter for a call captured on ``device`` that consumes
+    ``n`` counter values (the Philox ops through :func:`_take_offset`; the
+    attention dropout, ``ops/attention.py``, with n = 1). Inside
+    :class:`batched_offsets`: the counter tensor itself, and ``n`` joins what
+    the step-end add advances it by. Otherwise: a snapshot, and the counter
+    advances by ``n`` right away."""
     key = device.index
     base = _COUNTER.get(key)
     if base is None:
         raise RuntimeError("dropout inside a HIP-graph capture needs an eager warmup call first")
     if _BATCH[0] is not None:
-        _BATCH[0][key] = _BATCH[0].get(key, 0) + (n + 3) // 4
-        return seed, base
+        _BATCH[0][key] = _BATCH[0].get(key, 0) + n
+        return base
     used = base.clone()
-    base.add_((n + 3) // 4)
-    return seed, used
+    base.add_(n)
+    return used
 
 
 def _ensure_counter(device):

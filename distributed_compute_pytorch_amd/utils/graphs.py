@@ -15,6 +15,11 @@ Everything the step touches is capture-safe by construction:
   replays after the first (tools/graph_op_check.py), so zeroed accumulators
   come from fill kernels under capture and multi-tensor kernel tables are
   uploaded once, outside the graph, and kept alive for good;
+* every dropout draws fresh masks on every replay: host seeds are frozen into
+  the graph, so the Philox ops and the flash attention's dropout on the
+  probabilities both read the device counter of ``ops/dropout.py`` (the
+  attention as its seed offset), and the capture runs inside
+  ``batched_offsets``, whose one step-end add advances that counter;
 * the fused optimizers read hyper-parameters at capture time — changing the
   LR after capture requires re-capturing (``CapturedStep.recapture``).
 

@@ -900,6 +900,64 @@ std::vector<at::Tensor> conv3_bwd_fused(const at::Tensor& g, const at::Tensor& z
   return {dy2, acc2, dz3};
 }
 
+// conv3_bwd_fused at a downsample block, relu(bn3(z3) + bn_d(zd)): both BNs'
+// backward applies as the prologue (conv3_bwd.hip kDual / kDzd). Returns
+// (dy2, acc2, dz3, dzd) and, where the downsample conv is the stride-1 w → 4w
+// one (conv3_bwd_ds_mode 2; wdt = Wdᵀ bf16 [w][4w]), its data gradient dxd —
+// what bn_bwd_apply2_g followed by conv1x1_dgrad_bnred and conv1x1_dgrad return.
+std::vector<at::Tensor> conv3_bwd_ds_fused(const at::Tensor& g, const at::Tensor& z3, const at::Tensor& gamma3,
+                                           const at::Tensor& mean3, const at::Tensor& invstd3, const at::Tensor& acc3,
+                                           const at::Tensor& zd, const at::Tensor& gammad, const at::Tensor& meand,
+                                           const at::Tensor& invstdd, const at::Tensor& accd, const at::Tensor& wt,
+                                           const c10::optional<at::Tensor>& wdt, const at::Tensor& x2,
+                                           const c10::optional<at::Tensor>& gamma2,
+                                           const c10::optional<at::Tensor>& beta2, const at::Tensor& mean2,
+                                           const at::Tensor& invstd2) {
+  check_gemm_act(g, "conv3_bwd_ds_fused");
+  check_gemm_act(z3, "conv3_bwd_ds_fused");
+  check_gemm_act(zd, "conv3_bwd_ds_fused");
+  c10::hip::HIPGuard guard(g.device().index());
+  DK_CHECK(g.dim() == 4 && g.sizes() == z3.sizes() && g.sizes() == zd.sizes(),
+            "conv3_bwd_ds_fused: g and zd must match z3");
+  const int64_t C = g.size(1);
+  const int64_t M = g.numel() / C;
+  const int64_t w = C / 4;
+  const int mode = C % 4 == 0 ? kern::conv3_bwd_ds_mode(M, static_cast<int>(w)) : 0;
+  DK_CHECK(mode > 0, "conv3_bwd_ds_fused: unsupported shape");
+  auto wok = [&](const at::Tensor& t) {
+    return t.scalar_type() == at::kBFloat16 && t.is_contiguous() && t.numel() == w * C && t.device() == g.device();
+  };
+  DK_CHECK(wok(wt), "conv3_bwd_ds_fused: weight must be contiguous bf16 [w][4w]");
+  const bool dual = mode == 2;
+  DK_CHECK(!dual || (wdt.has_value() && wdt->defined() && wok(*wdt)),
+            "conv3_bwd_ds_fused: downsample weight must be contiguous bf16 [w][4w]");
+  auto f32c = [&](const at::Tensor& t, int64_t n) {
+    return t.scalar_type() == at::kFloat && t.numel() == n && t.is_contiguous() && t.device() == g.device();
+  };
+  DK_CHECK(f32c(gamma3, C) && f32c(mean3, C) && f32c(invstd3, C) && f32c(acc3, 2 * C) && f32c(gammad, C) &&
+                f32c(meand, C) && f32c(invstdd, C) && f32c(accd, 2 * C),
+            "conv3_bwd_ds_fused: gamma / mean / invstd fp32 [4w], acc fp32 [2*4w] for both BNs");
+  DK_CHECK(f32c(invstd2, w), "conv3_bwd_ds_fused: BN2 invstd fp32 [w]");
+  const BnRedIn r = bnred_in(x2, gamma2, beta2, mean2, invstd2, w, "conv3_bwd_ds_fused");
+  DK_CHECK(x2.numel() == M * w && x2.size(0) == g.size(0), "conv3_bwd_ds_fused: x2 / g pixel count mismatch");
+  at::Tensor dz3 = at::empty_like(z3, at::MemoryFormat::ChannelsLast);
+  at::Tensor dzd = at::empty_like(zd, at::MemoryFormat::ChannelsLast);
+  at::Tensor dy2 = at::empty_like(x2, at::MemoryFormat::ChannelsLast);
+  at::Tensor dxd;
+  if (dual) dxd = at::empty_like(x2, at::MemoryFormat::ChannelsLast);
+  auto s = stream_of(g);
+  at::Tensor acc2 = zeroed_floats(2 * w, g, s);
+  kern::conv3_bwd_ds_bf16(g.data_ptr(), z3.data_ptr(), zd.data_ptr(), wt.data_ptr(), dual ? wdt->data_ptr() : nullptr,
+                          x2.data_ptr(), dz3.data_ptr(), dzd.data_ptr(), dy2.data_ptr(),
+                          dual ? dxd.data_ptr() : nullptr, M, static_cast<int>(w), gamma3.data_ptr<float>(),
+                          mean3.data_ptr<float>(), invstd3.data_ptr<float>(), acc3.data_ptr<float>(),
+                          gammad.data_ptr<float>(), meand.data_ptr<float>(), invstdd.data_ptr<float>(),
+                          accd.data_ptr<float>(), r.w.defined() ? r.w.data_ptr<float>() : nullptr,
+                          r.b.defined() ? r.b.data_ptr<float>() : nullptr, r.mean, r.invstd, acc2.data_ptr<float>(), s);
+  if (dual) return {dy2, acc2, dz3, dzd, dxd};
+  return {dy2, acc2, dz3, dzd};
+}
+
 // (dweight, dbias) of a training BN from acc = (Σg, Σg·(x - mean)) alone: the
 // values bn_bwd_apply_g returns, for a node whose apply pass runs later
 std::vector<at::Tensor> bn_dparams(const at::Tensor& acc, const at::Tensor& invstd) {
@@ -2035,6 +2093,11 @@ void bind(pybind11::module& m) {
         "bottleneck conv3 backward with BN3's backward apply as its prologue -> (dy2, acc2, dz3)");
   m.def("conv3_bwd_mode", [](int64_t M, int64_t w) { return kern::conv3_bwd_mode(M, static_cast<int>(w)); },
         "0: conv3's backward of this shape stays unfused; 1: conv3_bwd_fused");
+  m.def("conv3_bwd_ds_fused", &conv3_bwd_ds_fused,
+        "conv3_bwd_fused at a downsample block: both BNs' backward applies as the prologue -> "
+        "(dy2, acc2, dz3, dzd[, dxd])");
+  m.def("conv3_bwd_ds_mode", [](int64_t M, int64_t w) { return kern::conv3_bwd_ds_mode(M, static_cast<int>(w)); },
+        "0: a downsample block of this shape stays on bn_bwd_apply2_g; 1: conv3_bwd_ds_fused without dxd; 2: with");
   m.def("bn_dparams", &bn_dparams, "(dweight, dbias) of a training BN from its backward reduction");
   m.def("conv1_fwd_fused", &conv1_fwd_fused,
         "block boundary relu(bn3(z3) + residual-or-bn_d(x2)) with the next conv1 fed from the same tile -> "

@@ -23,6 +23,14 @@
 // row tiles. BN3's dγ / dβ come from acc alone (bn_dparams_kernel: the apply
 // kernel's own expressions) because autograd needs them before this kernel's
 // node runs.
+//
+// Downsample blocks (relu(bn3(z3) + bn_d(zd)), MODE below): the boundary hands
+// the same g to two BNs. kDual (w = 64, stride-1 downsample conv of w → 4w
+// channels) also loads zd, forms dzd with bn_bwd_apply2_kernel's expressions,
+// stores it once and multiplies a second LDS image by Wdᵀ for the downsample
+// conv's data gradient dx_d (no RED: no BN behind that conv's input here):
+// g, z3, zd read once, dz3, dzd written once, neither re-read by a data-gradient
+// GEMM.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -40,6 +48,11 @@ constexpr int kBM = 32;  // rows per tile: g + z3 of one tile = 32 KB (w = 64) /
 // 1 = this kernel (dz3 stored for the weight gradient)
 int g_mode64 = 1;
 int g_mode128 = 1;
+// gemm_tune "c3bwd_ds64" / "c3bwd_ds128" ("c3bwd_ds" sets both): the downsample
+// blocks' variants: kDual at w = 64 (on: −0.85 ms per step), kDzd at w = 128
+// (off: inside the run-to-run spread alone; NOTES §39)
+int g_ds64 = 1;
+int g_ds128 = 0;
 // gemm_tune "c3bwd_grid": > 0 caps the persistent grid (tests: several tiles per workgroup)
 int g_grid = 0;
 
@@ -61,10 +74,24 @@ struct C3Args {
   float* stats;         // zeroed [2w]: += (Σg2, Σg2·(x2 − μ2))
   int64_t M;
   int tiles;
+  // downsample variants only
+  const uint16_t* zd;   // [M, 4w] the downsample BN's input
+  const uint16_t* wdt;  // [w][4w] Wdᵀ bf16 (kDual)
+  uint16_t* dzd;        // [M, 4w] out
+  uint16_t* dxd;        // [M, w] out (kDual): the downsample conv's data gradient
+  const float* gammad;  // downsample BN
+  const float* meand;
+  const float* invstdd;
+  const float* accd;    // (Σg, Σg·(zd − μd)) [2·4w]
 };
 
-template <int W>
-__global__ void __launch_bounds__(4 * W) conv3_bwd_kernel(const C3Args a) {
+// kPlain: identity blocks. kDzd: also forms and stores dzd. kDual: kDzd + the
+// downsample conv's data gradient from a second LDS image.
+enum { kPlain = 0, kDzd = 1, kDual = 2 };
+
+template <int W, int MODE>
+__global__ void __launch_bounds__(4 * W, MODE == kDual ? 2 : 1) conv3_bwd_kernel(const C3Args a) {
+  constexpr bool DS = MODE != kPlain, DUAL = MODE == kDual;
   constexpr int C = 4 * W;        // conv3 output channels = the data gradient's K
   constexpr int T = 4 * W;        // threads: one wave per 16 output channels
   constexpr int CPR = C / 8;      // 16-B chunks per row
@@ -73,7 +100,10 @@ __global__ void __launch_bounds__(4 * W) conv3_bwd_kernel(const C3Args a) {
   constexpr int KS = C / 32;      // MFMA k-steps
   constexpr int FM = kBM / 16;    // row fragments
   static_assert(RPP * NP == kBM && CPR >= 16, "tile shape");
-  __shared__ __attribute__((aligned(16))) char sA[kBM * C * 2];
+  constexpr int IMG = kBM * C * 2;  // one swizzled tile image
+  // kDual: the dzd image behind the dz3 image (32 KB at w = 64, two workgroups
+  // per CU use 64 of 160 KB) instead of one buffer and a third barrier per tile
+  __shared__ __attribute__((aligned(16))) char sA[IMG * (DUAL ? 2 : 1)];
 
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
   const int cc = t % CPR, r0 = t / CPR;
@@ -84,22 +114,61 @@ __global__ void __launch_bounds__(4 * W) conv3_bwd_kernel(const C3Args a) {
 
   // BN3 backward coefficients of this thread's 8 channels (bn_bwd_apply_kernel's expressions)
   float k1[8], k2[8], k3[8], mu[8];
+  // downsample variants: both BNs' coefficients [k1 | k2 | k3 | μ][C] × 2 stay
+  // in LDS (bn_bwd_apply2_kernel's expressions, the unfused path of these
+  // blocks): 64 resident VGPRs would not fit beside both weight slices under
+  // the 256 of two workgroups per CU (NOTES §39); a thread re-reads its 8
+  // channels' 256 B per tile
+  __shared__ __attribute__((aligned(16))) float sK[DS ? 8 * C : 4];
+  if constexpr (DS) {
+    const float inv_m = 1.f / static_cast<float>(M);
+    for (int c = t; c < C; c += T) {
+      const float i3 = a.invstd3[c], id = a.invstdd[c];
+      sK[c] = a.gamma3[c] * i3;
+      sK[C + c] = a.acc3[c] * inv_m;
+      sK[2 * C + c] = a.acc3[C + c] * inv_m * i3 * i3;
+      sK[3 * C + c] = a.mean3[c];
+      sK[4 * C + c] = a.gammad[c] * id;
+      sK[5 * C + c] = a.accd[c] * inv_m;
+      sK[6 * C + c] = a.accd[C + c] * inv_m * id * id;
+      sK[7 * C + c] = a.meand[c];
+    }
+    __syncthreads();
+  } else {
 #pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const int c = cc * 8 + k;
-    const float inv = a.invstd3[c];
-    const float sb = a.acc3[c], sg = a.acc3[C + c];
-    k1[k] = a.gamma3[c] * inv;
-    k2[k] = sb / static_cast<float>(M);
-    k3[k] = sg / static_cast<float>(M) * inv * inv;
-    mu[k] = a.mean3[c];
+    for (int k = 0; k < 8; ++k) {
+      const int c = cc * 8 + k;
+      const float inv = a.invstd3[c];
+      const float sb = a.acc3[c], sg = a.acc3[C + c];
+      k1[k] = a.gamma3[c] * inv;
+      k2[k] = sb / static_cast<float>(M);
+      k3[k] = sg / static_cast<float>(M) * inv * inv;
+      mu[k] = a.mean3[c];
+    }
   }
+  // a thread's 8 channels of coefficient set q (0: BN3, 1: the downsample BN) from LDS
+  auto coefs = [&](int q, float (&c1)[8], float (&c2)[8], float (&c3)[8], float (&cm)[8]) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const float* kp = sK + 4 * q * C + cc * 8 + 4 * h;
+      *reinterpret_cast<float4*>(c1 + 4 * h) = *reinterpret_cast<const float4*>(kp);
+      *reinterpret_cast<float4*>(c2 + 4 * h) = *reinterpret_cast<const float4*>(kp + C);
+      *reinterpret_cast<float4*>(c3 + 4 * h) = *reinterpret_cast<const float4*>(kp + 2 * C);
+      *reinterpret_cast<float4*>(cm + 4 * h) = *reinterpret_cast<const float4*>(kp + 3 * C);
+    }
+  };
   // this wave's 16 rows of W3ᵀ as MFMA A fragments: row 16wv + (lane&15), k = 32ks + 8(lane>>4) … +7
   bf16x8 wf[KS];
   {
     const uint16_t* wp = a.wt + static_cast<int64_t>(16 * wv + (lane & 15)) * C + 8 * (lane >> 4);
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) wf[ks] = *reinterpret_cast<const bf16x8*>(wp + 32 * ks);
+  }
+  bf16x8 wdf[DUAL ? KS : 1];  // and of Wdᵀ
+  if constexpr (DUAL) {
+    const uint16_t* wp = a.wdt + static_cast<int64_t>(16 * wv + (lane & 15)) * C + 8 * (lane >> 4);
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) wdf[ks] = *reinterpret_cast<const bf16x8*>(wp + 32 * ks);
   }
   // RED: this lane's 4 epilogue channels 16wv + 4(lane>>4) + r
   const int nc = 16 * wv + 4 * (lane >> 4);
@@ -115,7 +184,7 @@ __global__ void __launch_bounds__(4 * W) conv3_bwd_kernel(const C3Args a) {
     ssum[r] = ssq[r] = 0.f;
   }
 
-  uint4 gq[NP], zq[NP];
+  uint4 gq[NP], zq[NP], dq[DS ? NP : 1];
   uint2 xq[FM];
   // rows past M load row 0; they are zeroed / skipped where they are used
   auto load = [&](int tl) {
@@ -123,6 +192,16 @@ __global__ void __launch_bounds__(4 * W) conv3_bwd_kernel(const C3Args a) {
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
       const int64_t m = m0 + r0 + RPP * i;
+      if constexpr (DS) {
+        // rows past M load the tile's first row: an unsigned 32-bit lane offset
+        // on a uniform tile base (three more 64-bit lane addresses per pass do not fit)
+        const int rem = static_cast<int>(M - m0 < kBM ? M - m0 : kBM);
+        const uint32_t lo = (r0 + RPP * i < rem ? r0 + RPP * i : 0) * C + cc * 8;
+        gq[i] = ld16_nt(a.g + m0 * C + lo);
+        zq[i] = ld16_nt(a.z3 + m0 * C + lo);
+        dq[i] = ld16_nt(a.zd + m0 * C + lo);
+        continue;
+      }
       const int64_t o = (m < M ? m : 0) * C + cc * 8;
       gq[i] = ld16_nt(a.g + o);
       zq[i] = ld16_nt(a.z3 + o);
@@ -148,6 +227,7 @@ __global__ void __launch_bounds__(4 * W) conv3_bwd_kernel(const C3Args a) {
       const uint32_t g4[4] = {gq[i].x, gq[i].y, gq[i].z, gq[i].w};
       const uint32_t z4[4] = {zq[i].x, zq[i].y, zq[i].z, zq[i].w};
       float d[8];
+      if constexpr (DS) coefs(0, k1, k2, k3, mu);
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         const float gk = (k & 1) ? bf_hi(g4[k >> 1]) : bf_lo(g4[k >> 1]);
@@ -158,6 +238,23 @@ __global__ void __launch_bounds__(4 * W) conv3_bwd_kernel(const C3Args a) {
       if (m < M) st16_nt(a.dz3 + m * C + cc * 8, v);
       else v = make_uint4(0, 0, 0, 0);
       *reinterpret_cast<uint4*>(sA + row * (C * 2) + 16 * (cc ^ (row & 15))) = v;
+      if constexpr (DS) {
+        const uint32_t y4[4] = {dq[i].x, dq[i].y, dq[i].z, dq[i].w};
+        float e[8], j1[8], j2[8], j3[8], jm[8];
+        coefs(1, j1, j2, j3, jm);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const float gk = (k & 1) ? bf_hi(g4[k >> 1]) : bf_lo(g4[k >> 1]);
+          const float xk = (k & 1) ? bf_hi(y4[k >> 1]) : bf_lo(y4[k >> 1]);
+          e[k] = j1[k] * (gk - j2[k] - (xk - jm[k]) * j3[k]);
+        }
+        uint4 u = make_uint4(pack2(e[0], e[1]), pack2(e[2], e[3]), pack2(e[4], e[5]), pack2(e[6], e[7]));
+        if (m < M) st16_nt(a.dzd + m * C + cc * 8, u);
+        else u = make_uint4(0, 0, 0, 0);
+        if constexpr (DUAL) *reinterpret_cast<uint4*>(sA + IMG + row * (C * 2) + 16 * (cc ^ (row & 15))) = u;
+        // one pass at a time: interleaving the passes holds every unpacked operand at once
+        __builtin_amdgcn_sched_barrier(0);
+      }
     }
     uint2 xc[FM];
 #pragma unroll
@@ -194,6 +291,29 @@ __global__ void __launch_bounds__(4 * W) conv3_bwd_kernel(const C3Args a) {
           ssum[r] += gk;
           ssq[r] = fmaf(gk, xk - dmu[r], ssq[r]);
         }
+      }
+    }
+    if constexpr (DUAL) {
+      // the downsample conv's data gradient: the same loop on the dzd image against Wdᵀ
+      f32x4 ad[FM];
+#pragma unroll
+      for (int j = 0; j < FM; ++j) ad[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+#pragma unroll
+        for (int j = 0; j < FM; ++j) {
+          const int row = 16 * j + (lane & 15);
+          const bf16x8 xf = *reinterpret_cast<const bf16x8*>(sA + IMG + row * (C * 2) +
+                                                             16 * ((4 * ks + (lane >> 4)) ^ (row & 15)));
+          ad[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wdf[ks], xf, ad[j], 0, 0, 0);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < FM; ++j) {
+        const int64_t m = m0 + 16 * j + (lane & 15);
+        if (m < M)
+          *reinterpret_cast<uint2*>(a.dxd + m * W + nc) =
+              make_uint2(pack2(ad[j][0], ad[j][1]), pack2(ad[j][2], ad[j][3]));
       }
     }
     __syncthreads();  // every wave is done with the tile image
@@ -235,6 +355,9 @@ bool conv3_bwd_tune(const char* key, int value) {
   if (!strcmp(key, "c3bwd")) g_mode64 = g_mode128 = m;
   else if (!strcmp(key, "c3bwd64")) g_mode64 = m;
   else if (!strcmp(key, "c3bwd128")) g_mode128 = m;
+  else if (!strcmp(key, "c3bwd_ds")) g_ds64 = g_ds128 = m;
+  else if (!strcmp(key, "c3bwd_ds64")) g_ds64 = m;
+  else if (!strcmp(key, "c3bwd_ds128")) g_ds128 = m;
   else if (!strcmp(key, "c3bwd_grid")) g_grid = value < 0 ? 0 : value;
   else return false;
   return true;
@@ -244,6 +367,9 @@ int conv3_bwd_tune_get(const char* key) {
   if (!strcmp(key, "c3bwd")) return g_mode64 < g_mode128 ? g_mode64 : g_mode128;
   if (!strcmp(key, "c3bwd64")) return g_mode64;
   if (!strcmp(key, "c3bwd128")) return g_mode128;
+  if (!strcmp(key, "c3bwd_ds")) return g_ds64 < g_ds128 ? g_ds64 : g_ds128;
+  if (!strcmp(key, "c3bwd_ds64")) return g_ds64;
+  if (!strcmp(key, "c3bwd_ds128")) return g_ds128;
   if (!strcmp(key, "c3bwd_grid")) return g_grid;
   return -1;
 }
@@ -252,6 +378,19 @@ int conv3_bwd_mode(int64_t M, int w) {
   if (M <= 0 || M >= (int64_t(1) << 31)) return 0;
   return w == 64 ? g_mode64 : (w == 128 ? g_mode128 : 0);
 }
+
+int conv3_bwd_ds_mode(int64_t M, int w) {
+  if (conv3_bwd_mode(M, w) <= 0) return 0;  // c3bwd=0 turns everything off
+  return w == 64 ? (g_ds64 ? kDual : 0) : (g_ds128 ? kDzd : 0);
+}
+
+namespace {
+int c3_grid(int per_cu, int tiles) {
+  int P = 256 * per_cu;
+  if (g_grid > 0 && g_grid < P) P = g_grid;
+  return P > tiles ? tiles : P;
+}
+}  // namespace
 
 void conv3_bwd_bf16(const void* g, const void* z3, const void* wt, const void* x2, void* dz3, void* dy2, int64_t M,
                     int w, const float* gamma3, const float* mean3, const float* invstd3, const float* acc3,
@@ -277,11 +416,50 @@ void conv3_bwd_bf16(const void* g, const void* z3, const void* wt, const void* x
   a.tiles = static_cast<int>((M + kBM - 1) / kBM);
   // resident workgroups: w = 64 → 256 threads, 176 VGPRs: 2 per CU;
   // w = 128 → 512 threads, 216 VGPRs: 1 per CU (64 KB of g + z3 in flight per CU either way)
-  int P = 256 * (w == 64 ? 2 : 1);
-  if (g_grid > 0 && g_grid < P) P = g_grid;
-  if (P > a.tiles) P = a.tiles;
-  if (w == 64) hipLaunchKernelGGL(conv3_bwd_kernel<64>, dim3(P), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(conv3_bwd_kernel<128>, dim3(P), dim3(512), 0, s, a);
+  a.zd = a.wdt = nullptr;
+  a.dzd = a.dxd = nullptr;
+  a.gammad = a.meand = a.invstdd = a.accd = nullptr;
+  const int P = c3_grid(w == 64 ? 2 : 1, a.tiles);
+  if (w == 64) hipLaunchKernelGGL((conv3_bwd_kernel<64, kPlain>), dim3(P), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((conv3_bwd_kernel<128, kPlain>), dim3(P), dim3(512), 0, s, a);
+}
+
+void conv3_bwd_ds_bf16(const void* g, const void* z3, const void* zd, const void* wt, const void* wdt, const void* x2,
+                       void* dz3, void* dzd, void* dy2, void* dxd, int64_t M, int w, const float* gamma3,
+                       const float* mean3, const float* invstd3, const float* acc3, const float* gammad,
+                       const float* meand, const float* invstdd, const float* accd, const float* gamma2,
+                       const float* beta2, const float* mean2, const float* invstd2, float* stats, hipStream_t s) {
+  C3Args a;
+  a.g = static_cast<const uint16_t*>(g);
+  a.z3 = static_cast<const uint16_t*>(z3);
+  a.wt = static_cast<const uint16_t*>(wt);
+  a.x2 = static_cast<const uint16_t*>(x2);
+  a.dz3 = static_cast<uint16_t*>(dz3);
+  a.dy2 = static_cast<uint16_t*>(dy2);
+  a.gamma3 = gamma3;
+  a.mean3 = mean3;
+  a.invstd3 = invstd3;
+  a.acc3 = acc3;
+  a.gamma2 = gamma2;
+  a.beta2 = beta2;
+  a.mean2 = mean2;
+  a.invstd2 = invstd2;
+  a.stats = stats;
+  a.M = M;
+  a.tiles = static_cast<int>((M + kBM - 1) / kBM);
+  a.zd = static_cast<const uint16_t*>(zd);
+  a.wdt = static_cast<const uint16_t*>(wdt);
+  a.dzd = static_cast<uint16_t*>(dzd);
+  a.dxd = static_cast<uint16_t*>(dxd);
+  a.gammad = gammad;
+  a.meand = meand;
+  a.invstdd = invstdd;
+  a.accd = accd;
+  // w = 64 → kDual, 234 VGPRs: 2 workgroups per CU; w = 128 → kDzd, 242 VGPRs: 1 per CU
+  // (96 KB of g + z3 + zd in flight per CU either way)
+  const int P = c3_grid(w == 64 ? 2 : 1, a.tiles);
+  if (w == 64) hipLaunchKernelGGL((conv3_bwd_kernel<64, kDual>), dim3(P), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((conv3_bwd_kernel<128, kDzd>), dim3(P), dim3(512), 0, s, a);
 }
 
 void bn_dparams(const float* acc, const float* invstd, float* dgamma, float* dbeta, int C, hipStream_t s) {

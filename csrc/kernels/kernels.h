@@ -80,6 +80,20 @@ void conv3_bwd_bf16(const void* g, const void* z3, const void* wt, const void* x
 // 0 = this shape stays on the unfused path; 1 = conv3_bwd_bf16 (gemm_tune
 // "c3bwd" / "c3bwd64" / "c3bwd128"; "c3bwd_grid" caps the persistent grid)
 int conv3_bwd_mode(int64_t M, int w);
+// The same at a downsample block, relu(bn3(z3) + bn_d(zd)): both BNs' backward
+// applies (bn_bwd_apply2_kernel's expressions and rounding) as the prologue;
+// dz3 and dzd [M, 4w] are stored once. w = 64: also dxd [M, w] = dzd · Wd, the
+// data gradient of the stride-1 downsample conv (wdt = Wdᵀ bf16 [w][4w]);
+// w = 128: wdt / dxd unused (nullptr). accd = (Σg, Σg·(zd − μd)) [2·4w].
+void conv3_bwd_ds_bf16(const void* g, const void* z3, const void* zd, const void* wt, const void* wdt, const void* x2,
+                       void* dz3, void* dzd, void* dy2, void* dxd, int64_t M, int w, const float* gamma3,
+                       const float* mean3, const float* invstd3, const float* acc3, const float* gammad,
+                       const float* meand, const float* invstdd, const float* accd, const float* gamma2,
+                       const float* beta2, const float* mean2, const float* invstd2, float* stats, hipStream_t s);
+// 0 = a downsample block of this shape stays on bn_bwd_apply2; 1 = conv3_bwd_ds_bf16
+// without dxd (w = 128); 2 = with it (w = 64). gemm_tune "c3bwd_ds" / "c3bwd_ds64" /
+// "c3bwd_ds128"; 0 whenever conv3_bwd_mode is
+int conv3_bwd_ds_mode(int64_t M, int w);
 bool conv3_bwd_tune(const char* key, int value);  // false: not one of its keys
 int conv3_bwd_tune_get(const char* key);          // -1: not one of its keys
 // dgamma = Σg(x−μ)·invstd, dbeta = Σg from acc = (Σg, Σg·(x − μ)) [2C]

@@ -36,6 +36,13 @@ void conv3_bwd_bf16(const void*, const void*, const void*, const void*, void*, v
   gpu_only("conv3_bwd_bf16");
 }
 int conv3_bwd_mode(int64_t, int) { return 0; }
+void conv3_bwd_ds_bf16(const void*, const void*, const void*, const void*, const void*, const void*, void*, void*,
+                       void*, void*, int64_t, int, const float*, const float*, const float*, const float*,
+                       const float*, const float*, const float*, const float*, const float*, const float*,
+                       const float*, const float*, float*, hipStream_t) {
+  gpu_only("conv3_bwd_ds_bf16");
+}
+int conv3_bwd_ds_mode(int64_t, int) { return 0; }
 bool conv3_bwd_tune(const char*, int) { return false; }
 int conv3_bwd_tune_get(const char*) { return -1; }
 void bn_dparams(const float*, const float*, float*, float*, int, hipStream_t) { gpu_only("bn_dparams"); }

@@ -111,7 +111,16 @@ class _Conv1x1Fn(torch.autograd.Function):
         if gy is None:
             return None, None, None
         gy = _cl(gy)
-        dx = _C.conv1x1_dgrad(gy, wt) if ctx.needs_input_grad[0] else None
+        ds = _c3ds_take(ctx, gy, 1)
+        dx = None
+        if ds is not None:
+            # gy is the masked gradient g of a fused downsample boundary: the conv3
+            # backward kernel formed dzd and, at w = 64, this conv's data gradient
+            gy, dx = ds[3], ds[4]
+        if not ctx.needs_input_grad[0]:
+            dx = None
+        elif dx is None:
+            dx = _C.conv1x1_dgrad(gy, wt)
         dw = None
         if ctx.needs_input_grad[1]:
             dw = _C.conv1x1_wgrad(gy, x).view(ctx.wshape)
@@ -132,12 +141,91 @@ class _Conv1x1Fn(torch.autograd.Function):
 _C3_DEFERRED: dict = {}
 
 
-def _c3_put(g: torch.Tensor, z3, gamma, mean, invstd, acc) -> None:
+# The same at a downsample boundary, relu(bn3(z3) + bn_d(zd)) (conv3_bwd.hip
+# kDual / kDzd): g stands in for dz3 and for dzd. Autograd does not promise
+# which of the two producer nodes (conv3's, the downsample conv's; both marked
+# `_c3ds` at forward time) runs first: whichever does launches
+# `_C.conv3_bwd_ds_fused` with the conv3 node's saved operands and leaves the
+# results in the entry for its sibling, which then runs its weight gradient
+# only (w = 64) or its usual backward on dzd (w = 128).
+_C3DS_DEFERRED: dict = {}
+
+
+class _C3DSEntry:
+    __slots__ = ("ops", "c3node", "dsnode", "dual", "out", "taken", "shape", "dtype")
+
+    def __init__(self, ops, c3node, dsnode, dual):
+        self.ops, self.c3node, self.dsnode, self.dual = ops, c3node, dsnode, dual
+        self.out, self.taken = None, set()
+        self.shape, self.dtype = ops[0].shape, ops[0].dtype
+
+
+def _c3_none_pending() -> None:
+    """A block boundary is about to defer: every earlier deferred entry must
+    have been taken (by both nodes, at a downsample boundary)."""
     if _C3_DEFERRED:
         _C3_DEFERRED.clear()
+        _C3DS_DEFERRED.clear()
         raise RuntimeError("conv3 backward fusion: a deferred BN3 gradient of an earlier node was never taken by its "
                            "conv3 node (gemm_tune c3bwd=0 disables the fusion)")
+    if _C3DS_DEFERRED:
+        half = any(e.taken for e in _C3DS_DEFERRED.values())
+        _C3DS_DEFERRED.clear()
+        raise RuntimeError("conv3 backward fusion: the deferred gradient of an earlier downsample boundary was "
+                           + ("taken by only one of its two nodes" if half else "never taken by its nodes")
+                           + " (gemm_tune c3bwd_ds=0 disables the fusion)")
+
+
+def _c3_put(g: torch.Tensor, z3, gamma, mean, invstd, acc) -> None:
+    _c3_none_pending()
     _C3_DEFERRED[g.data_ptr()] = (g, z3, gamma, mean, invstd, acc)
+
+
+def _c3ds_put(g: torch.Tensor, ops, nodes) -> None:
+    _c3_none_pending()
+    c3node, dsnode, dual = nodes
+    _C3DS_DEFERRED[g.data_ptr()] = _C3DSEntry((g,) + tuple(ops), c3node, dsnode, dual)
+
+
+def _c3ds_take(ctx, gz: torch.Tensor, role: int):
+    """(dy2, acc2, dz3, dzd, dxd-or-None) of the downsample boundary whose
+    deferred gradient ``gz`` is, for a node marked at forward time (``role`` 0:
+    the conv3 node, 1: the downsample conv node), else None. The first of the
+    two nodes launches the kernel. A marked node that received any other
+    gradient (its output had another consumer and autograd summed the
+    gradients, or the entry is stale) raises."""
+    if not getattr(ctx, "_c3ds", False):
+        return None
+    key = gz.data_ptr()
+    e = _C3DS_DEFERRED.get(key)
+    if e is None or e.shape != gz.shape or e.dtype != gz.dtype or role in e.taken:
+        _C3DS_DEFERRED.clear()
+        raise RuntimeError("conv3 backward fusion: this node's output was handed to a fused downsample block "
+                           "boundary, but the gradient it received is not that boundary's deferred one (z3 or the "
+                           "downsample conv's output has another consumer?); gemm_tune c3bwd_ds=0 disables the fusion")
+    if e.out is None:
+        try:
+            wt, x, gamma2, beta2, mean2, invstd2 = _c3_node_operands(e.c3node)
+            wdt = e.dsnode.saved_tensors[1] if e.dual else None
+            out = _C.conv3_bwd_ds_fused(*e.ops, wt, wdt, x, gamma2, beta2, mean2, invstd2)
+        except Exception:
+            _C3DS_DEFERRED.clear()
+            raise
+        e.out = tuple(out) + (None,) * (5 - len(out))
+        e.ops = None
+    e.taken.add(role)
+    if len(e.taken) == 2:
+        del _C3DS_DEFERRED[key]
+    return e.out
+
+
+def _c3_node_operands(fn):
+    """(W3ᵀ, x2, gamma2, beta2, mean2, invstd2) from a conv3 node's saved tensors."""
+    if isinstance(fn, _BNReluConv1x1Fn._backward_cls):
+        x, gamma, beta, wt, mean, invstd, _, _ = fn.saved_tensors
+    else:
+        x, _, gamma, beta, mean, invstd, _, wt = fn.saved_tensors
+    return wt, x, gamma, beta, mean, invstd
 
 
 def _c3_take(ctx, gz: torch.Tensor):
@@ -156,27 +244,56 @@ def _c3_take(ctx, gz: torch.Tensor):
     return e[1:]
 
 
+def _c3_node(z3: torch.Tensor):
+    """The conv3 node that produced ``z3`` when its backward can run
+    conv3_bwd.hip, else None."""
+    fn = z3.grad_fn
+    if fn is None or not torch.is_grad_enabled() or z3.dtype != torch.bfloat16 or z3.dim() != 4:
+        return None
+    if isinstance(fn, _BNReluConv1x1Fn._backward_cls):
+        if not _PRO_RED:
+            return None
+    elif isinstance(fn, _BNReluConvFn._backward_cls):
+        if fn.cfg[0] != 1 or fn.cfg[1] != 1:
+            return None
+    else:
+        return None
+    c = z3.shape[1]
+    if c % 4 or not z3.is_contiguous(memory_format=torch.channels_last):
+        return None
+    return fn
+
+
 def _c3_defer_ok(z3: torch.Tensor) -> bool:
     """True (and the producing conv3 node is marked) when BN3's backward apply
     over ``z3`` can be deferred into that node's backward."""
-    fn = z3.grad_fn
-    if fn is None or not torch.is_grad_enabled() or z3.dtype != torch.bfloat16 or z3.dim() != 4:
-        return False
-    if isinstance(fn, _BNReluConv1x1Fn._backward_cls):
-        if not _PRO_RED:
-            return False
-    elif isinstance(fn, _BNReluConvFn._backward_cls):
-        if fn.cfg[0] != 1 or fn.cfg[1] != 1:
-            return False
-    else:
-        return False
+    fn = _c3_node(z3)
     c = z3.shape[1]
-    if c % 4 or not z3.is_contiguous(memory_format=torch.channels_last):
-        return False
-    if _C.conv3_bwd_mode(z3.numel() // c, c // 4) <= 0:
+    if fn is None or _C.conv3_bwd_mode(z3.numel() // c, c // 4) <= 0:
         return False
     fn._c3_defer = True
     return True
+
+
+def _c3ds_defer_ok(z3: torch.Tensor, zd: torch.Tensor):
+    """(conv3 node, downsample conv node, dual) — both nodes marked — when both
+    BNs' backward applies at the downsample boundary relu(bn3(z3) + bn_d(zd))
+    can be deferred into those nodes' backward, else None. ``dual`` (w = 64):
+    the downsample conv is the stride-1 1x1 w → 4w one and the kernel also
+    forms its data gradient."""
+    fn, fd = _c3_node(z3), zd.grad_fn
+    if (fn is None or fd is None or fd is fn or not _APPLY2 or zd.shape != z3.shape or zd.dtype != z3.dtype
+            or not zd.is_contiguous(memory_format=torch.channels_last)):
+        return None
+    c = z3.shape[1]
+    mode = _C.conv3_bwd_ds_mode(z3.numel() // c, c // 4)
+    if mode == 2:
+        if not isinstance(fd, _Conv1x1Fn._backward_cls) or tuple(fd.wshape) != (c, c // 4, 1, 1):
+            return None
+    elif mode != 1 or not isinstance(fd, (_Conv1x1Fn._backward_cls, _ConvKxKGemmFn._backward_cls)):
+        return None
+    fn._c3ds = fd._c3ds = True
+    return fn, fd, mode == 2
 
 
 # BN-prologue 1x1 conv (ResNet layer-1 conv3): BN backward reduce in the dgrad
@@ -205,14 +322,17 @@ class _BNReluConv1x1Fn(torch.autograd.Function):
             return (None,) * 11
         gz = _cl(gz)
         d3 = _c3_take(ctx, gz)
+        ds = _c3ds_take(ctx, gz, 0)
         if d3 is not None:
             # gz is the masked gradient g of BN3's output: BN3's backward apply
             # runs as the data-gradient kernel's prologue, which also stores dz3
             da, acc, gz = _C.conv3_bwd_fused(gz, *d3, wt, x, gamma, beta, mean, invstd)
+        elif ds is not None:  # the same at a downsample boundary
+            da, acc, gz = ds[:3]
         dw = _C.conv1x1_wgrad(gz, x, scale, shift, True).view(ctx.wshape)
         if dw.dtype != ctx.wdtype:
             dw = dw.to(ctx.wdtype)
-        if d3 is not None:
+        if d3 is not None or ds is not None:
             dx, dgamma, dbeta = _C.bn_act_bwd_apply(da, x, gamma, beta, mean, invstd, acc)
         elif _PRO_RED:
             # BN+ReLU backward reduction in the data-gradient GEMM's epilogue
@@ -306,6 +426,7 @@ class _BNResActConv1x1Fn(torch.autograd.Function):
                 stats2, momentum, eps, momentum2, eps2, defer=False):
         ctx.set_materialize_grads(False)
         ctx.defer = bool(defer) and x2 is None
+        ctx.defer_ds = defer if (defer and x2 is not None) else None  # (conv3 node, downsample conv node, dual)
         if not RES_PROLOGUE and _c1_fused_ok(z3, gamma, beta, stats, residual if x2 is None else x2, gamma2, beta2,
                                              stats2, w_next):
             # y formed once per element in the kernel that multiplies it by W1
@@ -353,7 +474,14 @@ class _BNResActConv1x1Fn(torch.autograd.Function):
         dw = _C.conv1x1_wgrad(gz, y)
         g, acc, acc2 = _C.conv1x1_dgrad_resred(gz, wt, z3, None if gy is None else _cl(gy), mean, bits, x2, mean2)
         dres = dx2 = dgamma2 = dbeta2 = None
-        if x2 is not None and _APPLY2:  # both BNs' apply passes share one read of g
+        if x2 is not None and _APPLY2 and ctx.defer_ds:
+            # downsample block whose conv3 / downsample conv nodes form dz3 and dzd
+            # themselves (conv3_bwd.hip): g stands in for both
+            _c3ds_put(g, (z3, gamma, mean, invstd, acc, x2, gamma2, mean2, invstd2, acc2), ctx.defer_ds)
+            dz3 = dx2 = g
+            dgamma, dbeta = _C.bn_dparams(acc, invstd)
+            dgamma2, dbeta2 = _C.bn_dparams(acc2, invstd2)
+        elif x2 is not None and _APPLY2:  # both BNs' apply passes share one read of g
             dz3, dgamma, dbeta, dx2, dgamma2, dbeta2 = _C.bn_bwd_apply2_g(g, z3, gamma, mean, invstd, acc, x2, gamma2,
                                                                           mean2, invstd2, acc2)
         elif ctx.defer:
@@ -393,7 +521,7 @@ def bn_res_act_conv1x1(bn3, z3: torch.Tensor, s3: torch.Tensor, identity: Option
         return _BNResActConv1x1Fn.apply(z3, bn3.weight, bn3.bias, None, x2, bn_d.weight, bn_d.bias, w_next,
                                         bn3.running_mean, bn3.running_var, _nbt(bn3), s3, bn_d.running_mean,
                                         bn_d.running_var, _nbt(bn_d), s2, bn3.momentum, bn3.eps, bn_d.momentum,
-                                        bn_d.eps)
+                                        bn_d.eps, None if RES_PROLOGUE else _c3ds_defer_ok(z3, x2))
     return _BNResActConv1x1Fn.apply(z3, bn3.weight, bn3.bias, identity, None, None, None, w_next, bn3.running_mean,
                                     bn3.running_var, _nbt(bn3), s3, None, None, None, None, bn3.momentum, bn3.eps,
                                     0.0, 0.0, not RES_PROLOGUE and _c3_defer_ok(z3))
@@ -450,8 +578,11 @@ class _BNReluConvFn(torch.autograd.Function):
         k, stride, pad, wshape, wdtype = ctx.cfg
         gz = _cl(gz)
         d3 = _c3_take(ctx, gz)
-        if d3 is not None:  # marked nodes are 1x1 stride 1; gz is BN3's masked gradient g (conv3_bwd.hip)
-            dy, acc, gz = _C.conv3_bwd_fused(gz, *d3, wt, x, gamma, beta, mean, invstd)
+        ds = _c3ds_take(ctx, gz, 0)
+        if d3 is not None or ds is not None:
+            # marked nodes are 1x1 stride 1; gz is BN3's masked gradient g (conv3_bwd.hip)
+            dy, acc, gz = (_C.conv3_bwd_fused(gz, *d3, wt, x, gamma, beta, mean, invstd) if d3 is not None
+                           else ds[:3])
             dw = _C.conv1x1_wgrad(gz, y).view(wshape)
         elif k == 1 and stride == 1:
             dw = _C.conv1x1_wgrad(gz, y).view(wshape)
@@ -581,6 +712,9 @@ class _ConvKxKGemmFn(torch.autograd.Function):
         x, w, wd = ctx.saved_tensors
         s, p, wdtype = ctx.cfg
         gy = _cl(gy)
+        ds = _c3ds_take(ctx, gy, 1)
+        if ds is not None:  # gy is a fused downsample boundary's masked gradient g: dzd from the conv3 backward kernel
+            gy = ds[3]
         kh, kw = w.shape[2], w.shape[3]
         dx = dw = None
         if ctx.needs_input_grad[1]:

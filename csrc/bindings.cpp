@@ -236,6 +236,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("grad_scale"), pybind11::arg("shadows") = std::vector<at::Tensor>{},
         pybind11::arg("steps") = std::vector<at::Tensor>{});
   m.def("fused_adadelta", &ops::fused_adadelta);
+  m.def("fused_lamb", &ops::fused_lamb, py::arg("params"), py::arg("grads"), py::arg("exp_avgs"),
+        py::arg("exp_avg_sqs"), py::arg("lr"), py::arg("beta1"), py::arg("beta2"), py::arg("eps"),
+        py::arg("weight_decay"), py::arg("step"), py::arg("bias_correction"), py::arg("always_adapt"),
+        py::arg("maximize"), py::arg("grad_scale"), py::arg("clip") = py::none(),
+        py::arg("shadows") = std::vector<at::Tensor>{}, py::arg("steps") = std::vector<at::Tensor>{},
+        "LAMB over a tensor list; returns the per-tensor trust ratios (fp32, parameters' device)");
+  m.def("fused_lars", &ops::fused_lars, py::arg("params"), py::arg("grads"), py::arg("bufs"), py::arg("lr"),
+        py::arg("momentum"), py::arg("dampening"), py::arg("weight_decay"), py::arg("nesterov"), py::arg("maximize"),
+        py::arg("first_step"), py::arg("trust_coefficient"), py::arg("eps"), py::arg("always_adapt"),
+        py::arg("grad_scale"),
+        "LARS over a tensor list; returns the per-tensor local learning rates (fp32, parameters' device)");
   m.def("sumsq", &ops::sumsq);
   m.def("scale_by", &ops::scale_by);
   m.def("table_cache_size", &ops::table_cache_size);

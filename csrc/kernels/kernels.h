@@ -53,6 +53,40 @@ void emb_small_bwd(const int64_t* idx, const float* g, float* gw, int64_t M, int
 // In-place scale of every tensor: x *= scale_dev[0] (device scalar).
 void mt_scale_by(TableView t, int64_t nchunks, DType d, const float* scale_dev, hipStream_t s);
 
+// Layer-wise adaptive optimizers (LAMB / LARS): three launches over one table.
+// A norm pass writes two fp32 partial sums per chunk, partials[2c] = Σp² and
+// partials[2c + 1] = Σu² (LAMB: u = the Adam-style update; LARS: the scaled
+// gradient), indexed by the global chunk number c, so the result does not
+// depend on the grid; a reduce pass (one workgroup per tensor, fixed order, no
+// atomics) turns them into the tensor's trust ratio, stored through
+// `ratio_list`: a table list of one fp32 slot per tensor; the update pass
+// reads it back. Every partial and slot is rewritten on each call. A group
+// that does not adapt skips the norm pass and gets ratio 1.
+struct LambParams {
+  float lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, grad_scale;
+  // 1 - beta rounded from double: 1.f - 0.999f is off by 5e-5 relative, which
+  // would scale v (and, without bias correction, u) by that much
+  float omb1, omb2;
+  bool maximize, adapt, shadow;
+  // >= 0: table list of per-tensor device fp32 `step` scalars (capturable
+  // mode, as mt_adam); < 0: bc1 / bc2_sqrt above are used
+  int step_list;
+  int ratio_list;
+};
+// lists: 0 param, 1 grad, 2 exp_avg, 3 exp_avg_sq, then (shadow) a bf16 copy of
+// the updated parameter, then the step and ratio lists. clip: optional device
+// fp32 scalar multiplied into grad_scale (nullptr = 1). partials: fp32 [2 * nchunks].
+void mt_lamb(TableView t, int64_t nchunks, DType p, const LambParams& a, const float* clip, float* partials,
+             hipStream_t s);
+
+struct LarsParams {
+  float lr, momentum, dampening, wd, grad_scale, trust, eps;
+  bool nesterov, maximize, first_step, has_buf, adapt;
+  int ratio_list;
+};
+// lists: 0 param, 1 grad, 2 momentum buffer (has_buf), then the ratio list.
+void mt_lars(TableView t, int64_t nchunks, DType p, const LarsParams& a, float* partials, hipStream_t s);
+
 // dst[i] = src[i], i < n, with the words carried in KERNEL ARGUMENTS (src is
 // host memory read at launch / capture time; 256 words per launch). Used for
 // table uploads inside a HIP-graph capture: a captured memcpy node is not

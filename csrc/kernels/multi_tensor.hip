@@ -459,6 +459,294 @@ __global__ void __launch_bounds__(kThreads) mt_scale_by_kernel(Tab tab, int64_t 
   });
 }
 
+// ---------------------------------------------------------- LAMB / LARS ---
+// Layer-wise trust ratios need ‖p‖ and ‖u‖ per tensor in the middle of the
+// update. Pass 1 forms the update in registers and writes Σp², Σu² of each
+// chunk to partials[2c], partials[2c + 1] (c = global chunk number: the same
+// values whatever the grid size or its wrap at kMaxGrid); pass 2 sums a
+// tensor's partials in a fixed order and stores its ratio; pass 3 recomputes
+// the update with pass 1's code and applies it. No float atomics anywhere:
+// the same inputs give the same bits.
+
+// Workgroup sums of a and b in a fixed order: wave butterfly, then the 4 waves
+// through LDS. Every thread returns the totals. All threads must call it.
+__device__ __forceinline__ void block_sum2(float& a, float& b, float (*sm)[2]) {
+  a = wave_sum(a);
+  b = wave_sum(b);
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  __syncthreads();  // readers of the previous call are done
+  if (lane == 0) {
+    sm[wid][0] = a;
+    sm[wid][1] = b;
+  }
+  __syncthreads();
+  a = ((sm[0][0] + sm[1][0]) + sm[2][0]) + sm[3][0];
+  b = ((sm[0][1] + sm[1][1]) + sm[2][1]) + sm[3][1];
+}
+
+// grad_scale · clip, negated under maximize (clip: device scalar, nullptr = 1)
+__device__ __forceinline__ float signed_gscale(float grad_scale, bool maximize, const float* clip) {
+  float s = grad_scale;
+  if (clip) s *= *clip;
+  return maximize ? -s : s;
+}
+
+__device__ __forceinline__ void lamb_bias(LambParams& a, const Tab& tab, int t) {
+  if (a.step_list >= 0) {
+    const float step = *static_cast<const float*>(tab.ptr(a.step_list, t));
+    a.bc1 = 1.f - powf(a.beta1, step);
+    a.bc2_sqrt = sqrtf(1.f - powf(a.beta2, step));
+  }
+}
+
+// New moments and u = (m/bc1) / (sqrt(v)/bc2_sqrt + eps) + wd·p. Shared by the
+// norm and the update pass, so both see the same u.
+__device__ __forceinline__ float lamb_u(float p, float g, float& m, float& v, float gs, const LambParams& a) {
+  g *= gs;
+  m = fmaf(a.omb1, g - m, m);
+  v = fmaf(a.beta2, v, a.omb2 * g * g);
+  const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
+  return fmaf(a.wd, p, (m / a.bc1) / denom);
+}
+
+template <int PD>
+__global__ void __launch_bounds__(kThreads) mt_lamb_norms(Tab tab, int64_t nchunks, LambParams a0, const float* clip,
+                                                          float* __restrict__ partials) {
+  using A = Acc<PD>;
+  __shared__ float sm[kThreads / 64][2];
+  const float gs = signed_gscale(a0.grad_scale, a0.maximize, clip);
+  for_each_chunk(tab, nchunks, [&](int t, int64_t base, int64_t len) {
+    LambParams a = a0;
+    lamb_bias(a, tab, t);
+    const void* P = tab.ptr(0, t);
+    const void* G = tab.ptr(1, t);
+    const void* M = tab.ptr(2, t);
+    const void* V = tab.ptr(3, t);
+    const int vb = A::kVecBytes;
+    const size_t es = sizeof(typename A::S);
+    const bool vec = aligned(static_cast<const char*>(P) + base * es, vb) &&
+                     aligned(static_cast<const char*>(G) + base * es, vb) &&
+                     aligned(static_cast<const char*>(M) + base * es, vb) &&
+                     aligned(static_cast<const char*>(V) + base * es, vb);
+    float sp = 0.f, su = 0.f;  // at most kChunk / kThreads = 32 terms each
+    int64_t i0 = 0;
+    if (vec) {
+      const int64_t nv = len >> 2;
+      for (int64_t w = threadIdx.x; w < nv; w += kThreads) {
+        const int64_t i = base + 4 * w;
+        float p[4], g[4], m[4], v[4];
+        A::ld4(P, i, p);
+        A::ld4(G, i, g);
+        A::ld4(M, i, m);
+        A::ld4(V, i, v);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const float u = lamb_u(p[k], g[k], m[k], v[k], gs, a);
+          sp = fmaf(p[k], p[k], sp);
+          su = fmaf(u, u, su);
+        }
+      }
+      i0 = nv << 2;
+    }
+    for (int64_t j = i0 + threadIdx.x; j < len; j += kThreads) {
+      const int64_t i = base + j;
+      const float p = A::ld(P, i);
+      float m = A::ld(M, i), v = A::ld(V, i);
+      const float u = lamb_u(p, A::ld(G, i), m, v, gs, a);
+      sp = fmaf(p, p, sp);
+      su = fmaf(u, u, su);
+    }
+    block_sum2(sp, su, sm);
+    if (threadIdx.x == 0) {
+      const int64_t c = tab.chunk0(t) + base / kChunk;
+      partials[2 * c] = sp;
+      partials[2 * c + 1] = su;
+    }
+  });
+}
+
+template <int PD>
+__global__ void __launch_bounds__(kThreads) mt_lamb_update(Tab tab, int64_t nchunks, LambParams a0,
+                                                           const float* clip) {
+  using A = Acc<PD>;
+  const float gs = signed_gscale(a0.grad_scale, a0.maximize, clip);
+  for_each_chunk(tab, nchunks, [&](int t, int64_t base, int64_t len) {
+    LambParams a = a0;
+    lamb_bias(a, tab, t);
+    const float step_size = a.lr * *static_cast<const float*>(tab.ptr(a.ratio_list, t));
+    void* P = tab.ptr(0, t);
+    const void* G = tab.ptr(1, t);
+    void* M = tab.ptr(2, t);
+    void* V = tab.ptr(3, t);
+    void* SB = a.shadow ? tab.ptr(4, t) : nullptr;
+    using SH = Acc<BF16>;
+    const int vb = A::kVecBytes;
+    const size_t es = sizeof(typename A::S);
+    const bool vec = aligned(static_cast<char*>(P) + base * es, vb) &&
+                     aligned(static_cast<const char*>(G) + base * es, vb) &&
+                     aligned(static_cast<char*>(M) + base * es, vb) && aligned(static_cast<char*>(V) + base * es, vb) &&
+                     (!SB || aligned(static_cast<char*>(SB) + base * 2, 8));
+    int64_t i0 = 0;
+    if (vec) {
+      const int64_t nv = len >> 2;
+      for (int64_t w = threadIdx.x; w < nv; w += kThreads) {
+        const int64_t i = base + 4 * w;
+        float p[4], g[4], m[4], v[4];
+        A::ld4(P, i, p);
+        A::ld4(G, i, g);
+        A::ld4(M, i, m);
+        A::ld4(V, i, v);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const float u = lamb_u(p[k], g[k], m[k], v[k], gs, a);
+          p[k] = fmaf(-step_size, u, p[k]);
+        }
+        A::st4(P, i, p);
+        A::st4(M, i, m);
+        A::st4(V, i, v);
+        if (SB) SH::st4(SB, i, p);
+      }
+      i0 = nv << 2;
+    }
+    for (int64_t j = i0 + threadIdx.x; j < len; j += kThreads) {
+      const int64_t i = base + j;
+      float p = A::ld(P, i), m = A::ld(M, i), v = A::ld(V, i);
+      const float u = lamb_u(p, A::ld(G, i), m, v, gs, a);
+      p = fmaf(-step_size, u, p);
+      A::st(P, i, p);
+      A::st(M, i, m);
+      A::st(V, i, v);
+      if (SB) SH::st(SB, i, p);
+    }
+  });
+}
+
+// Per-tensor reduce of the partials of chunk0(t) … chunk0(t+1)-1 and the trust
+// ratio. One workgroup per tensor: strided serial sums (a tensor may have more
+// chunks than the workgroup has threads), then block_sum2's fixed tree.
+struct RatioArgs {
+  bool lars, adapt;
+  float trust, wd, eps;  // LARS only
+  int ratio_list;
+};
+
+__global__ void __launch_bounds__(kThreads) mt_lamb_ratio(Tab tab, const float* __restrict__ partials, RatioArgs a) {
+  __shared__ float sm[kThreads / 64][2];
+  for (int t = blockIdx.x; t < tab.n; t += gridDim.x) {
+    float sp = 0.f, sx = 0.f;
+    if (a.adapt) {  // uniform: the barriers inside are reached by all or none
+      const int64_t c1 = tab.chunk0(t + 1);
+      for (int64_t c = tab.chunk0(t) + threadIdx.x; c < c1; c += kThreads) {
+        sp += partials[2 * c];
+        sx += partials[2 * c + 1];
+      }
+      block_sum2(sp, sx, sm);
+    }
+    if (threadIdx.x == 0) {
+      float r = 1.f;
+      const float pn = sqrtf(sp), xn = sqrtf(sx);
+      if (a.adapt && pn > 0.f && xn > 0.f) r = a.lars ? a.trust * pn / (xn + a.wd * pn + a.eps) : pn / xn;
+      *static_cast<float*>(tab.ptr(a.ratio_list, t)) = r;
+    }
+  }
+}
+
+template <int PD>
+__global__ void __launch_bounds__(kThreads) mt_lars_norms(Tab tab, int64_t nchunks, LarsParams a,
+                                                          float* __restrict__ partials) {
+  using A = Acc<PD>;
+  __shared__ float sm[kThreads / 64][2];
+  const float gs = signed_gscale(a.grad_scale, a.maximize, nullptr);
+  for_each_chunk(tab, nchunks, [&](int t, int64_t base, int64_t len) {
+    const void* P = tab.ptr(0, t);
+    const void* G = tab.ptr(1, t);
+    const size_t es = sizeof(typename A::S);
+    const bool vec = aligned(static_cast<const char*>(P) + base * es, A::kVecBytes) &&
+                     aligned(static_cast<const char*>(G) + base * es, A::kVecBytes);
+    float sp = 0.f, sg = 0.f;
+    int64_t i0 = 0;
+    if (vec) {
+      const int64_t nv = len >> 2;
+      for (int64_t w = threadIdx.x; w < nv; w += kThreads) {
+        float p[4], g[4];
+        A::ld4(P, base + 4 * w, p);
+        A::ld4(G, base + 4 * w, g);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const float gk = gs * g[k];
+          sp = fmaf(p[k], p[k], sp);
+          sg = fmaf(gk, gk, sg);
+        }
+      }
+      i0 = nv << 2;
+    }
+    for (int64_t j = i0 + threadIdx.x; j < len; j += kThreads) {
+      const float p = A::ld(P, base + j), g = gs * A::ld(G, base + j);
+      sp = fmaf(p, p, sp);
+      sg = fmaf(g, g, sg);
+    }
+    block_sum2(sp, sg, sm);
+    if (threadIdx.x == 0) {
+      const int64_t c = tab.chunk0(t) + base / kChunk;
+      partials[2 * c] = sp;
+      partials[2 * c + 1] = sg;
+    }
+  });
+}
+
+// d = local·(g + wd·p), then torch SGD's momentum / dampening / nesterov /
+// first-step logic on d
+__device__ __forceinline__ void lars_elem(float& p, float g, float* b, float gs, float local, const LarsParams& a) {
+  float d = local * fmaf(a.wd, p, gs * g);
+  if (a.has_buf) {
+    const float nb = a.first_step ? d : fmaf(a.momentum, *b, (1.f - a.dampening) * d);
+    *b = nb;
+    d = a.nesterov ? fmaf(a.momentum, nb, d) : nb;
+  }
+  p = fmaf(-a.lr, d, p);
+}
+
+template <int PD>
+__global__ void __launch_bounds__(kThreads) mt_lars_update(Tab tab, int64_t nchunks, LarsParams a) {
+  using A = Acc<PD>;
+  const float gs = signed_gscale(a.grad_scale, a.maximize, nullptr);
+  for_each_chunk(tab, nchunks, [&](int t, int64_t base, int64_t len) {
+    const float local = *static_cast<const float*>(tab.ptr(a.ratio_list, t));
+    void* P = tab.ptr(0, t);
+    const void* G = tab.ptr(1, t);
+    void* B = a.has_buf ? tab.ptr(2, t) : nullptr;
+    const int vb = A::kVecBytes;
+    const size_t es = sizeof(typename A::S);
+    const bool vec = aligned(static_cast<char*>(P) + base * es, vb) &&
+                     aligned(static_cast<const char*>(G) + base * es, vb) &&
+                     (!B || aligned(static_cast<char*>(B) + base * es, vb));
+    int64_t i0 = 0;
+    if (vec) {
+      const int64_t nv = len >> 2;
+      for (int64_t w = threadIdx.x; w < nv; w += kThreads) {
+        const int64_t i = base + 4 * w;
+        float p[4], g[4], b[4] = {0.f, 0.f, 0.f, 0.f};
+        A::ld4(P, i, p);
+        A::ld4(G, i, g);
+        if (B && !a.first_step) A::ld4(B, i, b);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) lars_elem(p[k], g[k], &b[k], gs, local, a);
+        A::st4(P, i, p);
+        if (B) A::st4(B, i, b);
+      }
+      i0 = nv << 2;
+    }
+    for (int64_t j = i0 + threadIdx.x; j < len; j += kThreads) {
+      const int64_t i = base + j;
+      float p = A::ld(P, i);
+      float b = (B && !a.first_step) ? A::ld(B, i) : 0.f;
+      lars_elem(p, A::ld(G, i), &b, gs, local, a);
+      A::st(P, i, p);
+      if (B) A::st(B, i, b);
+    }
+  });
+}
+
 constexpr int kArgWords = 256;
 struct ArgWords {
   int64_t w[kArgWords];
@@ -532,6 +820,35 @@ void mt_scale_by(TableView t, int64_t nchunks, DType d, const float* scale_dev, 
   DK_DISPATCH_DTYPE(d, D,
       hipLaunchKernelGGL((mt_scale_by_kernel<D>), grid_for(nchunks), dim3(kThreads), 0, s, tab_of(t), nchunks,
                          scale_dev));
+}
+
+void mt_lamb(TableView t, int64_t nchunks, DType p, const LambParams& a, const float* clip, float* partials,
+             hipStream_t s) {
+  if (nchunks <= 0) return;
+  const dim3 tgrid(static_cast<unsigned>(t.n < kMaxGrid ? t.n : kMaxGrid));
+  if (a.adapt) {
+    DK_DISPATCH_DTYPE(p, PD,
+        hipLaunchKernelGGL((mt_lamb_norms<PD>), grid_for(nchunks), dim3(kThreads), 0, s, tab_of(t), nchunks, a, clip,
+                           partials));
+  }
+  hipLaunchKernelGGL(mt_lamb_ratio, tgrid, dim3(kThreads), 0, s, tab_of(t), partials,
+                     RatioArgs{false, a.adapt, 0.f, 0.f, 0.f, a.ratio_list});
+  DK_DISPATCH_DTYPE(p, PD,
+      hipLaunchKernelGGL((mt_lamb_update<PD>), grid_for(nchunks), dim3(kThreads), 0, s, tab_of(t), nchunks, a, clip));
+}
+
+void mt_lars(TableView t, int64_t nchunks, DType p, const LarsParams& a, float* partials, hipStream_t s) {
+  if (nchunks <= 0) return;
+  const dim3 tgrid(static_cast<unsigned>(t.n < kMaxGrid ? t.n : kMaxGrid));
+  if (a.adapt) {
+    DK_DISPATCH_DTYPE(p, PD,
+        hipLaunchKernelGGL((mt_lars_norms<PD>), grid_for(nchunks), dim3(kThreads), 0, s, tab_of(t), nchunks, a,
+                           partials));
+  }
+  hipLaunchKernelGGL(mt_lamb_ratio, tgrid, dim3(kThreads), 0, s, tab_of(t), partials,
+                     RatioArgs{true, a.adapt, a.trust, a.wd, a.eps, a.ratio_list});
+  DK_DISPATCH_DTYPE(p, PD,
+      hipLaunchKernelGGL((mt_lars_update<PD>), grid_for(nchunks), dim3(kThreads), 0, s, tab_of(t), nchunks, a));
 }
 
 void copy_words(const int64_t* src, int64_t* dst, int64_t n, hipStream_t s) {

@@ -376,6 +376,229 @@ void fused_adadelta(const TensorList& params, const TensorList& grads, const Ten
   }
 }
 
+// ----------------------------------------------------------- LAMB / LARS ---
+namespace {
+
+// The ratio tensor (one fp32 per input tensor) and its 1-element views: passed
+// as a table list, so each kernel reaches its tensor's slot by table index
+// although get_table drops empty tensors. Empty tensors keep ratio 1.
+at::Tensor ratio_slots(const TensorList& params, TensorList& slots) {
+  const int64_t n = static_cast<int64_t>(params.size());
+  bool any_empty = false;
+  for (auto& p : params) any_empty = any_empty || p.numel() == 0;
+  const auto opt = at::TensorOptions().dtype(at::kFloat).device(params[0].device());
+  at::Tensor ratio = any_empty ? at::ones({n}, opt) : at::empty({n}, opt);
+  slots.reserve(n);
+  for (int64_t i = 0; i < n; ++i) slots.push_back(ratio.narrow(0, i, 1));
+  return ratio;
+}
+
+void check_same_dtype(const std::vector<const TensorList*>& lists, const char* what) {
+  const auto dt = (*lists[0])[0].scalar_type();
+  for (auto* l : lists)
+    for (auto& t : *l) DK_CHECK(t.scalar_type() == dt, what, ": one dtype per call (parameters, gradients and state)");
+}
+
+int64_t chunks_of(int64_t n) { return (n + kern::kChunk - 1) / kern::kChunk; }
+
+// CPU norms: double sums per kChunk chunk, added in chunk order, so the result
+// does not depend on the thread count. f(i, sp, sx) adds element i's terms.
+template <class F>
+void chunked_sumsq2(int64_t n, double& sp, double& sx, F&& f) {
+  const int64_t nch = chunks_of(n);
+  std::vector<double> part(2 * nch, 0.0);
+  at::parallel_for(0, nch, 1, [&](int64_t c0, int64_t c1) {
+    for (int64_t c = c0; c < c1; ++c) {
+      double a = 0.0, b = 0.0;
+      const int64_t e = std::min(n, (c + 1) * kern::kChunk);
+      for (int64_t i = c * kern::kChunk; i < e; ++i) f(i, a, b);
+      part[2 * c] = a;
+      part[2 * c + 1] = b;
+    }
+  });
+  sp = sx = 0.0;
+  for (int64_t c = 0; c < nch; ++c) {
+    sp += part[2 * c];
+    sx += part[2 * c + 1];
+  }
+}
+
+}  // namespace
+
+at::Tensor fused_lamb(const TensorList& params, const TensorList& grads, const TensorList& exp_avgs,
+                      const TensorList& exp_avg_sqs, double lr, double beta1, double beta2, double eps,
+                      double weight_decay, double step, bool bias_correction, bool always_adapt, bool maximize,
+                      double grad_scale, const c10::optional<at::Tensor>& clip, const TensorList& shadows,
+                      const TensorList& steps) {
+  if (params.empty()) return at::empty({0}, at::kFloat);
+  std::vector<const TensorList*> lists{&params, &grads, &exp_avgs, &exp_avg_sqs};
+  const bool shadow = !shadows.empty();
+  if (shadow) {
+    lists.push_back(&shadows);
+    DK_CHECK(shadows.size() == params.size(), "fused_lamb: one shadow per parameter");
+    for (size_t i = 0; i < shadows.size(); ++i)
+      DK_CHECK(shadows[i].scalar_type() == at::kBFloat16 && params[i].scalar_type() == at::kFloat &&
+                    shadows[i].is_contiguous() && params[i].is_contiguous(),
+                "fused_lamb: shadows must be contiguous bf16 copies of contiguous fp32 params");
+  }
+  check_lists(lists, "fused_lamb");
+  check_same_dtype({&params, &grads, &exp_avgs, &exp_avg_sqs}, "fused_lamb");
+  if (clip.has_value())
+    DK_CHECK(clip->scalar_type() == at::kFloat && clip->numel() == 1 && clip->device() == params[0].device(),
+              "fused_lamb: clip must be a 1-element fp32 tensor on the parameters' device");
+  const bool adapt = weight_decay != 0.0 || always_adapt;
+  // device step scalars (capturable mode) only matter to the bias corrections
+  int step_list = -1;
+  if (!steps.empty()) {
+    DK_CHECK(steps.size() == params.size() && on_gpu(params), "fused_lamb: steps must be one device tensor per param");
+    for (auto& t : steps)
+      DK_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.numel() == 1 && t.device() == params[0].device(),
+                "fused_lamb: each step must be a 1-element fp32 tensor on the parameters' device");
+    if (bias_correction) {
+      step_list = static_cast<int>(lists.size());
+      lists.push_back(&steps);
+    }
+  }
+  const double bc1 = bias_correction ? 1.0 - std::pow(beta1, step) : 1.0;
+  const double bc2_sqrt = bias_correction ? std::sqrt(1.0 - std::pow(beta2, step)) : 1.0;
+  if (on_gpu(params)) {
+    c10::hip::HIPGuard guard(params[0].device().index());
+    TensorList slots;
+    at::Tensor ratio = ratio_slots(params, slots);
+    const int ratio_list = static_cast<int>(lists.size());
+    lists.push_back(&slots);
+    auto tab = get_table(lists);
+    at::Tensor partials = at::empty({2 * std::max<int64_t>(tab.nchunks, 1)}, ratio.options());
+    kern::LambParams a{static_cast<float>(lr), static_cast<float>(beta1), static_cast<float>(beta2),
+                       static_cast<float>(eps), static_cast<float>(weight_decay), static_cast<float>(bc1),
+                       static_cast<float>(bc2_sqrt), static_cast<float>(grad_scale), static_cast<float>(1.0 - beta1),
+                       static_cast<float>(1.0 - beta2), maximize, adapt, shadow, step_list, ratio_list};
+    kern::mt_lamb(kern::TableView{tab.dev.data_ptr<int64_t>(), tab.n}, tab.nchunks, kdtype(params[0].scalar_type()),
+                  a, clip.has_value() ? clip->data_ptr<float>() : nullptr, partials.data_ptr<float>(),
+                  cur_stream(params[0]));
+    return ratio;
+  }
+  at::Tensor ratio = at::ones({static_cast<int64_t>(params.size())}, at::kFloat);
+  float* rp = ratio.data_ptr<float>();
+  float gs = static_cast<float>(grad_scale);
+  if (clip.has_value()) gs *= *clip->data_ptr<float>();
+  if (maximize) gs = -gs;
+  const float flr = static_cast<float>(lr), b1 = static_cast<float>(beta1), b2 = static_cast<float>(beta2);
+  const float feps = static_cast<float>(eps), wd = static_cast<float>(weight_decay);
+  const float fbc1 = static_cast<float>(bc1), fbc2 = static_cast<float>(bc2_sqrt);
+  const float omb1 = static_cast<float>(1.0 - beta1), omb2 = static_cast<float>(1.0 - beta2);
+  for (size_t t = 0; t < params.size(); ++t) {
+    const int64_t n = params[t].numel();
+    if (n == 0) continue;
+    AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, params[t].scalar_type(), "cpu_lamb", [&] {
+      scalar_t* p = P<scalar_t>(params[t]);
+      const scalar_t* g = P<scalar_t>(grads[t]);
+      scalar_t* m = P<scalar_t>(exp_avgs[t]);
+      scalar_t* v = P<scalar_t>(exp_avg_sqs[t]);
+      // the new moments and u of element i; both passes go through it
+      auto elem = [&](int64_t i, float& mv, float& vv) {
+        const float gv = static_cast<float>(g[i]) * gs;
+        mv = static_cast<float>(m[i]);
+        vv = static_cast<float>(v[i]);
+        mv = mv + omb1 * (gv - mv);
+        vv = b2 * vv + omb2 * gv * gv;
+        const float denom = std::sqrt(vv) / fbc2 + feps;
+        return (mv / fbc1) / denom + wd * static_cast<float>(p[i]);
+      };
+      float r = 1.f;
+      if (adapt) {
+        double sp, su;
+        chunked_sumsq2(n, sp, su, [&](int64_t i, double& a, double& b) {
+          float mv, vv;
+          const double u = elem(i, mv, vv), pv = static_cast<float>(p[i]);
+          a += pv * pv;
+          b += u * u;
+        });
+        if (sp > 0.0 && su > 0.0) r = static_cast<float>(std::sqrt(sp) / std::sqrt(su));
+      }
+      rp[t] = r;
+      at::parallel_for(0, n, 16384, [&](int64_t s, int64_t e) {
+        for (int64_t i = s; i < e; ++i) {
+          float mv, vv;
+          const float u = elem(i, mv, vv);
+          p[i] = static_cast<scalar_t>(static_cast<float>(p[i]) - flr * r * u);
+          m[i] = static_cast<scalar_t>(mv);
+          v[i] = static_cast<scalar_t>(vv);
+        }
+      });
+    });
+  }
+  for (size_t t = 0; t < shadows.size(); ++t) shadows[t].copy_(params[t]);
+  return ratio;
+}
+
+at::Tensor fused_lars(const TensorList& params, const TensorList& grads, const TensorList& bufs, double lr,
+                      double momentum, double dampening, double weight_decay, bool nesterov, bool maximize,
+                      bool first_step, double trust_coefficient, double eps, bool always_adapt, double grad_scale) {
+  if (params.empty()) return at::empty({0}, at::kFloat);
+  const bool has_buf = momentum != 0.0;
+  std::vector<const TensorList*> lists{&params, &grads};
+  if (has_buf) lists.push_back(&bufs);
+  check_lists(lists, "fused_lars");
+  check_same_dtype(lists, "fused_lars");
+  const bool adapt = weight_decay != 0.0 || always_adapt;
+  if (on_gpu(params)) {
+    c10::hip::HIPGuard guard(params[0].device().index());
+    TensorList slots;
+    at::Tensor ratio = ratio_slots(params, slots);
+    const int ratio_list = static_cast<int>(lists.size());
+    lists.push_back(&slots);
+    auto tab = get_table(lists);
+    at::Tensor partials = at::empty({2 * std::max<int64_t>(tab.nchunks, 1)}, ratio.options());
+    kern::LarsParams a{static_cast<float>(lr), static_cast<float>(momentum), static_cast<float>(dampening),
+                       static_cast<float>(weight_decay), static_cast<float>(grad_scale),
+                       static_cast<float>(trust_coefficient), static_cast<float>(eps), nesterov, maximize,
+                       first_step, has_buf, adapt, ratio_list};
+    kern::mt_lars(kern::TableView{tab.dev.data_ptr<int64_t>(), tab.n}, tab.nchunks, kdtype(params[0].scalar_type()),
+                  a, partials.data_ptr<float>(), cur_stream(params[0]));
+    return ratio;
+  }
+  at::Tensor ratio = at::ones({static_cast<int64_t>(params.size())}, at::kFloat);
+  float* rp = ratio.data_ptr<float>();
+  const float gs = maximize ? -static_cast<float>(grad_scale) : static_cast<float>(grad_scale);
+  const float flr = static_cast<float>(lr), mom = static_cast<float>(momentum), damp = static_cast<float>(dampening);
+  const float wd = static_cast<float>(weight_decay);
+  for (size_t t = 0; t < params.size(); ++t) {
+    const int64_t n = params[t].numel();
+    if (n == 0) continue;
+    AT_DISPATCH_FLOATING_TYPES_AND2(at::kBFloat16, at::kHalf, params[t].scalar_type(), "cpu_lars", [&] {
+      scalar_t* p = P<scalar_t>(params[t]);
+      const scalar_t* g = P<scalar_t>(grads[t]);
+      scalar_t* b = has_buf ? P<scalar_t>(bufs[t]) : nullptr;
+      float local = 1.f;
+      if (adapt) {
+        double sp, sg;
+        chunked_sumsq2(n, sp, sg, [&](int64_t i, double& a, double& c) {
+          const double pv = static_cast<float>(p[i]), gv = static_cast<float>(g[i]) * gs;
+          a += pv * pv;
+          c += gv * gv;
+        });
+        const double pn = std::sqrt(sp), gn = std::sqrt(sg);
+        if (pn > 0.0 && gn > 0.0) local = static_cast<float>(trust_coefficient * pn / (gn + weight_decay * pn + eps));
+      }
+      rp[t] = local;
+      at::parallel_for(0, n, 16384, [&](int64_t s, int64_t e) {
+        for (int64_t i = s; i < e; ++i) {
+          const float pv = static_cast<float>(p[i]);
+          float d = local * (static_cast<float>(g[i]) * gs + wd * pv);
+          if (has_buf) {
+            const float bv = first_step ? d : mom * static_cast<float>(b[i]) + (1.f - damp) * d;
+            b[i] = static_cast<scalar_t>(bv);
+            d = nesterov ? d + mom * bv : bv;
+          }
+          p[i] = static_cast<scalar_t>(pv - flr * d);
+        }
+      });
+    });
+  }
+  return ratio;
+}
+
 // ------------------------------------------------------------- grad norm ---
 at::Tensor sumsq(const TensorList& tensors) {
   DK_CHECK(!tensors.empty(), "sumsq: empty list");

@@ -28,6 +28,25 @@ void fused_adadelta(const TensorList& params, const TensorList& grads, const Ten
                     const TensorList& acc_deltas, double lr, double rho, double eps, double weight_decay,
                     bool maximize, double grad_scale);
 
+// LAMB (You et al. 2019): u = (m/bc1) / (sqrt(v)/bc2_sqrt + eps) + wd·p,
+// p -= lr · r · u with the per-tensor trust ratio r = ‖p‖/‖u‖ (1 when a norm
+// is 0, or when weight_decay == 0 and !always_adapt). clip: optional
+// 1-element fp32 tensor on the parameters' device, multiplied into
+// grad_scale. Returns the fp32 ratios, one per input tensor (1 for empty
+// tensors), on the parameters' device.
+at::Tensor fused_lamb(const TensorList& params, const TensorList& grads, const TensorList& exp_avgs,
+                      const TensorList& exp_avg_sqs, double lr, double beta1, double beta2, double eps,
+                      double weight_decay, double step, bool bias_correction, bool always_adapt, bool maximize,
+                      double grad_scale, const c10::optional<at::Tensor>& clip = c10::nullopt,
+                      const TensorList& shadows = {}, const TensorList& steps = {});
+
+// LARS (You et al. 2017) on torch SGD's momentum logic: d = local·(g + wd·p)
+// with local = trust_coefficient·‖p‖/(‖g‖ + wd·‖p‖ + eps) (1 under the same
+// rule as LAMB's ratio). Returns the per-tensor local rates like fused_lamb.
+at::Tensor fused_lars(const TensorList& params, const TensorList& grads, const TensorList& bufs, double lr,
+                      double momentum, double dampening, double weight_decay, bool nesterov, bool maximize,
+                      bool first_step, double trust_coefficient, double eps, bool always_adapt, double grad_scale);
+
 // Returns a 2-element fp32 tensor on the tensors' device: [sum of squares, nonfinite flag].
 at::Tensor sumsq(const TensorList& tensors);
 

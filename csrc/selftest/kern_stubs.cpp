@@ -29,6 +29,8 @@ void mt_adadelta(TableView, int64_t, DType, float, float, float, float, bool, fl
 }
 void mt_sumsq(TableView, int64_t, DType, float*, hipStream_t) { gpu_only("mt_sumsq"); }
 void mt_scale_by(TableView, int64_t, DType, const float*, hipStream_t) { gpu_only("mt_scale_by"); }
+void mt_lamb(TableView, int64_t, DType, const LambParams&, const float*, float*, hipStream_t) { gpu_only("mt_lamb"); }
+void mt_lars(TableView, int64_t, DType, const LarsParams&, float*, hipStream_t) { gpu_only("mt_lars"); }
 void copy_words(const int64_t*, int64_t*, int64_t, hipStream_t) { gpu_only("copy_words"); }
 void conv3_bwd_bf16(const void*, const void*, const void*, const void*, void*, void*, int64_t, int, const float*,
                     const float*, const float*, const float*, const float*, const float*, const float*, const float*,

@@ -583,6 +583,231 @@ class Adadelta(_DropsDeferred, Optimizer):
                                   group["maximize"], grad_scale)
 
 
+class LAMB(_DropsDeferred, Optimizer):
+    """LAMB (You et al. 2019, "Large Batch Optimization for Deep Learning"),
+    fused: per (device, dtype) class one norm launch, one per-tensor reduce and
+    one update launch over the whole parameter list.
+
+    ``u = (m/bc1) / (sqrt(v)/bc2_sqrt + eps) + weight_decay·p`` and
+    ``p -= lr · r · u`` with the layer's trust ratio ``r = ‖p‖/‖u‖``. ``r`` is 1
+    when either norm is 0, and for a group that does not adapt: one with
+    ``weight_decay == 0`` unless ``always_adapt=True``. Biases and LayerNorm /
+    BatchNorm parameters are kept out of adaptation the usual way::
+
+        decay = [p for n, p in model.named_parameters() if p.ndim > 1]
+        rest = [p for n, p in model.named_parameters() if p.ndim <= 1]
+        opt = LAMB([{"params": decay}, {"params": rest, "weight_decay": 0.0}], lr=2e-3)
+
+    State per parameter: ``step``, ``exp_avg``, ``exp_avg_sq`` (Adam's keys and
+    dtypes). ``bias_correction=False`` sets ``bc1 = bc2_sqrt = 1``.
+    ``capturable`` is Adam's flag: the ``step`` counters live on the device and
+    the kernels derive the bias corrections from them, so a step captured in a
+    HIP graph keeps advancing on replay; without it, stepping inside a capture
+    raises. The first step (state creation) must be eager in either mode.
+
+    ``max_grad_norm > 0`` scales the gradients by ``min(1, max_grad_norm /
+    (‖g‖ + 1e-6))``, ``‖g‖`` the L2 norm of ``grad_scale`` · every gradient of
+    every group. The factor stays on the device (no host sync), but a global
+    norm needs every gradient bucket, so with
+    ``DistributedDataParallel(overlap_optimizer=True)`` the step first waits for
+    all deferred reductions and the optimizer overlap is given up.
+
+    The norms are reduced in a fixed order without float atomics: the same
+    state and gradients give the same bits on every run. That holds with
+    ``max_grad_norm=0`` only; the global gradient norm is accumulated with a
+    float atomic.
+    """
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-6, weight_decay: float = 0.01,
+                 *, bias_correction: bool = True, always_adapt: bool = False, max_grad_norm: float = 0.0,
+                 maximize: bool = False, capturable: bool = False):
+        if lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"Invalid betas: {betas}")
+        if max_grad_norm < 0.0:
+            raise ValueError(f"Invalid max_grad_norm: {max_grad_norm}")
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, bias_correction=bias_correction,
+                        always_adapt=always_adapt, max_grad_norm=max_grad_norm, maximize=maximize,
+                        capturable=capturable)
+        super().__init__(params, defaults)
+
+    @torch.no_grad()
+    def step(self, closure=None, grad_scale: float = 1.0):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self._grad_norm = self._global_grad_norm(grad_scale)
+        try:
+            shadowed = [p for sh in _run_chunks(self, self._step, grad_scale) for p in sh]
+        finally:
+            self._grad_norm = None
+        _PARAM_EPOCH[0] += 1
+        for p in shadowed:  # rewritten by the kernel: valid for the new epoch
+            e = _BF16_SHADOWS[p]
+            e[1], e[2] = _PARAM_EPOCH[0], p._version
+        return loss
+
+    def _global_grad_norm(self, grad_scale):
+        """‖grad_scale · all gradients‖ as a device scalar, None when no group
+        clips."""
+        if not any(g["max_grad_norm"] > 0 for g in self.param_groups):
+            return None
+        sync_deferred_gradients()
+        by = defaultdict(list)
+        for group in self.param_groups:
+            for p in group["params"]:
+                if _grads_ok(p):
+                    by[p.device].append(_grad(p))
+        total = None
+        for gl in by.values():
+            ss = _C.sumsq(gl)[0]
+            total = ss if total is None else total + ss.to(total.device)
+        return None if total is None else total.sqrt() * abs(float(grad_scale))
+
+    def _step(self, ids, grad_scale):
+        """Update the parameters whose id is in ``ids`` (None: all); returns the
+        parameters whose bf16 shadow the kernel rewrote."""
+        capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+        shadowed = []
+        for group in self.param_groups:
+            cap_mode = group.get("capturable", False)
+            if capturing and not cap_mode:
+                raise RuntimeError("LAMB stepped inside HIP-graph capture without capturable=True: the bias "
+                                   "corrections would be frozen at their capture-time step. Construct the "
+                                   "optimizer with capturable=True (or set group['capturable'] = True before the "
+                                   "eager warmup steps).")
+            b1, b2 = group["betas"]
+            clip = None
+            norm = getattr(self, "_grad_norm", None)
+            if group["max_grad_norm"] > 0 and norm is not None:
+                clip = torch.clamp(group["max_grad_norm"] / (norm + 1e-6), max=1.0)
+                clip = clip.reshape(1).to(torch.float32)
+            buckets = {}
+            for p in _chunk_params(self, group, ids):
+                if not _grads_ok(p):
+                    continue
+                st = self.state[p]
+                dev_step = cap_mode and p.is_cuda
+                if len(st) == 0:
+                    if capturing:
+                        # captured zeros would reset the state on every replay
+                        raise RuntimeError("capturable LAMB: run one eager step before capture (creates the state)")
+                    st["step"] = (torch.zeros((), dtype=torch.float32, device=p.device) if dev_step
+                                  else torch.tensor(0.0, dtype=torch.float32))
+                    st["exp_avg"] = _state_like(p)
+                    st["exp_avg_sq"] = _state_like(p)
+                elif dev_step and not st["step"].is_cuda:
+                    if capturing:
+                        raise RuntimeError("capturable LAMB: run one eager step before capture (moves 'step' "
+                                           "to the device)")
+                    st["step"] = st["step"].to(device=p.device, dtype=torch.float32)
+                elif not dev_step and st["step"].is_cuda:
+                    st["step"] = st["step"].cpu()
+                if dev_step:
+                    stepv = None
+                else:
+                    st["step"] += 1
+                    stepv = float(st["step"])
+                sh = _BF16_SHADOWS.get(p) if p.is_cuda else None
+                bk = buckets.get((p.device, p.dtype, stepv, sh is not None))
+                if bk is None:
+                    bk = buckets[(p.device, p.dtype, stepv, sh is not None)] = ([], [], [], [], [], [])
+                P, G, M, V, S, ST = bk
+                P.append(p)
+                G.append(_dense_like(_grad(p), p))
+                M.append(st["exp_avg"])
+                V.append(st["exp_avg_sq"])
+                if sh is not None:
+                    S.append(sh[0])
+                if dev_step:
+                    ST.append(st["step"].view(1))
+            for (dev, _, stepv, _), (P, G, M, V, S, ST) in buckets.items():
+                if ST:
+                    torch._foreach_add_(ST, 1.0)  # one launch; the kernels read the advanced steps
+                _C.fused_lamb(P, G, M, V, group["lr"], b1, b2, group["eps"], group["weight_decay"],
+                              0.0 if stepv is None else stepv, group["bias_correction"], group["always_adapt"],
+                              group["maximize"], grad_scale, None if clip is None else clip.to(dev), S, ST)
+                if S:
+                    shadowed.extend(P)
+        return shadowed
+
+
+class LARS(_DropsDeferred, Optimizer):
+    """LARS (You et al. 2017, "Large Batch Training of Convolutional
+    Networks") on torch.optim.SGD's update, fused like :class:`LAMB`.
+
+    ``d = local · (g + weight_decay·p)`` with the layer's local rate ``local =
+    trust_coefficient · ‖p‖ / (‖g‖ + weight_decay·‖p‖ + eps)``, then SGD's
+    momentum / dampening / nesterov logic on ``d`` (state key
+    ``momentum_buffer``) and ``p -= lr · d``. ``local`` is 1 when either norm
+    is 0, and for a group with ``weight_decay == 0`` unless
+    ``always_adapt=True``; biases and BatchNorm parameters go there::
+
+        decay = [p for n, p in model.named_parameters() if p.ndim > 1]
+        rest = [p for n, p in model.named_parameters() if p.ndim <= 1]
+        opt = LARS([{"params": decay, "weight_decay": 5e-5}, {"params": rest}], lr=10.0, momentum=0.9)
+
+    The norms are reduced in a fixed order without float atomics, so a step is
+    bitwise repeatable. First step and HIP-graph capture behave as in
+    :class:`SGD`.
+    """
+
+    def __init__(self, params, lr: float, momentum: float = 0.9, dampening: float = 0.0, weight_decay: float = 0.0,
+                 nesterov: bool = False, *, trust_coefficient: float = 0.001, eps: float = 1e-8,
+                 always_adapt: bool = False, maximize: bool = False):
+        if lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
+                        trust_coefficient=trust_coefficient, eps=eps, always_adapt=always_adapt, maximize=maximize)
+        super().__init__(params, defaults)
+
+    @torch.no_grad()
+    def step(self, closure=None, grad_scale: float = 1.0):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        _run_chunks(self, self._step, grad_scale)
+        _PARAM_EPOCH[0] += 1
+        return loss
+
+    def _step(self, ids, grad_scale):
+        """Update the parameters whose id is in ``ids`` (None: all)."""
+        capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+        for group in self.param_groups:
+            mom = group["momentum"]
+            buckets = defaultdict(lambda: ([], [], []))
+            for p in _chunk_params(self, group, ids):
+                if not _grads_ok(p):
+                    continue
+                st = self.state[p]
+                first = False
+                if mom != 0 and st.get("momentum_buffer") is None:
+                    if capturing:
+                        # as SGD: a captured "first step" flag would re-initialise
+                        # the buffer on every replay
+                        if group["dampening"] != 0:
+                            raise RuntimeError("LARS with dampening cannot take its first step inside HIP-graph "
+                                               "capture: run one eager step (warmup) before capturing")
+                        st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    else:
+                        st["momentum_buffer"] = torch.empty_like(p, memory_format=torch.preserve_format)
+                        first = True
+                P, G, B = buckets[(p.device, p.dtype, first)]
+                P.append(p)
+                G.append(_dense_like(_grad(p), p))
+                if mom != 0:
+                    B.append(st["momentum_buffer"])
+            for (dev, dt, first), (P, G, B) in buckets.items():
+                _C.fused_lars(P, G, B, group["lr"], mom, group["dampening"], group["weight_decay"],
+                              group["nesterov"], group["maximize"], first, group["trust_coefficient"],
+                              group["eps"], group["always_adapt"], grad_scale)
+
+
 @torch.no_grad()
 def clip_grad_norm_(parameters: Iterable[torch.Tensor], max_norm: float, eps: float = 1e-6) -> torch.Tensor:
     """Total-L2-norm gradient clipping without a host sync: one sum-of-squares

@@ -137,6 +137,47 @@ def main():
             ms = timeit(lambda: opt.step(), a.iters)
             rec(f"fused AdamW {name} ({nel / 1e6:.1f}M params, one launch)", ms, nel * 4 * 7)
         del m
+
+    # Layer-wise optimizers next to the elementwise ones they replace at large
+    # batch, on the same parameter lists and back to back: LAMB vs AdamW over
+    # BERT-base, LARS vs SGD over ResNet-50. "op" rows time the bare _C call
+    # (GPU time of the launches), "step" rows the optimizer's step() with its
+    # host work. Bytes: AdamW 7 and LAMB 11 fp32 words per parameter (LAMB's
+    # norm pass reads p, g, m, v once more); SGD 5 and LARS 7 (p, g again).
+    from distributed_compute_pytorch_amd.models import bert_base
+
+    def no_decay_split(ps):
+        return [{"params": [p for p in ps if p.ndim > 1]},
+                {"params": [p for p in ps if p.ndim <= 1], "weight_decay": 0.0}]
+
+    for name, m, pair in [("bert-base", bert_base(), ("AdamW", "LAMB")), ("resnet50", resnet50(), ("SGD", "LARS"))]:
+        ps = [torch.nn.Parameter(p.detach().to(dev)) for p in m.parameters()]
+        del m
+        for p in ps:
+            p.grad = torch.randn_like(p)
+        gs = [p.grad for p in ps]
+        nel = sum(p.numel() for p in ps)
+        tag = f"{name} ({nel / 1e6:.1f}M params)"
+        s1 = [torch.zeros_like(p) for p in ps]
+        s2 = [torch.zeros_like(p) for p in ps]
+        if pair[1] == "LAMB":
+            ops = [("AdamW", 7, lambda: _C.fused_adam(ps, gs, s1, s2, [], 1e-4, 0.9, 0.999, 1e-8, 0.01, 10.0, False,
+                                                      True, False, 1.0)),
+                   ("LAMB", 11, lambda: _C.fused_lamb(ps, gs, s1, s2, 1e-4, 0.9, 0.999, 1e-6, 0.01, 10.0, True, False,
+                                                      False, 1.0))]
+            opts = [("AdamW", 7, dcp.optim.AdamW(no_decay_split(ps), lr=1e-4, weight_decay=0.01)),
+                    ("LAMB", 11, dcp.optim.LAMB(no_decay_split(ps), lr=1e-4, weight_decay=0.01))]
+        else:
+            ops = [("SGD-momentum", 5, lambda: _C.fused_sgd(ps, gs, s1, 0.1, 0.9, 0.0, 1e-4, False, False, False,
+                                                            1.0)),
+                   ("LARS", 7, lambda: _C.fused_lars(ps, gs, s1, 0.1, 0.9, 0.0, 1e-4, False, False, False, 1e-3, 1e-8,
+                                                     False, 1.0))]
+            opts = [("SGD-momentum", 5, dcp.optim.SGD(no_decay_split(ps), lr=0.1, momentum=0.9, weight_decay=1e-4)),
+                    ("LARS", 7, dcp.optim.LARS(no_decay_split(ps), lr=0.1, momentum=0.9, weight_decay=1e-4))]
+        for label, words, fn in ops:
+            rec(f"fused {label} op {tag}", timeit(fn, a.iters), nel * 4 * words)
+        for label, words, opt in opts:
+            rec(f"fused {label} step {tag}", timeit(lambda: opt.step(), a.iters), nel * 4 * words)
     if a.json:
         with open(a.json, "w") as f:
             json.dump(res, f, indent=1)

@@ -16,6 +16,9 @@ void bind(pybind11::module& m);
 namespace convnet {
 void bind(pybind11::module& m);
 }
+namespace llama {
+void bind(pybind11::module& m);
+}
 }  // namespace dcp
 #include "trace/trace.h"
 #include "store/tcp_store.h"
@@ -259,4 +262,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   fused::bind(m);
   stem::bind(m);
   convnet::bind(m);
+  llama::bind(m);
 }

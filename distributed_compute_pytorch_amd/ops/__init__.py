@@ -7,8 +7,11 @@ from .pool import FusedMaxPool2d, fused_max_pool2d, relu_max_pool2d_dropout
 from .dropout import FusedDropout, FusedDropout2d, dropout_add, fused_dropout, fused_feature_dropout
 from .softmax import fused_log_softmax
 from .convnet import convnet_features, fc32
+from .rmsnorm import FusedRMSNorm, fused_rms_norm
+from .rope import apply_rope_qkv, rope_table
+from .swiglu import swiglu
 
 __all__ = ["BatchNormAct1d", "BatchNormAct2d", "bn_act", "FusedLayerNorm", "fused_layer_norm", "fused_cross_entropy",
            "FusedDropout", "FusedDropout2d", "dropout_add", "fused_dropout", "fused_feature_dropout",
            "FusedMaxPool2d", "fused_max_pool2d", "relu_max_pool2d_dropout", "fused_log_softmax", "EvalMetrics",
-           "convnet_features", "fc32"]
+           "convnet_features", "fc32", "FusedRMSNorm", "fused_rms_norm", "apply_rope_qkv", "rope_table", "swiglu"]

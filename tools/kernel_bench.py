@@ -35,10 +35,77 @@ def timeit(fn, iters):
     return s.elapsed_time(e) / iters
 
 
+def llama_ops(rec, iters, dev):
+    """RMSNorm / RoPE / SwiGLU kernels next to the stock PyTorch composition of
+    each op (back to back, same tensors) and, as the yardstick on the same
+    box, the LayerNorm kernels at the same shapes. Bytes: the analytic minimum
+    of the fused op (RMSNorm fwd bf16 4 B/elem; SwiGLU fwd 6 B per output
+    element; RoPE in place 2 × 2/3 of the packed bytes), also charged to the
+    stock rows so their TB/s reads as "effective"."""
+    from distributed_compute_pytorch_amd.ops.rope import rope_qkv_reference, rope_table
+
+    bf = torch.bfloat16
+
+    def stock_rms(x, w):
+        xf = x.float()
+        return (xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + 1e-6) * w).to(x.dtype)
+
+    for rows, D in [(8192, 768), (16384, 1024)]:
+        x = torch.randn(rows, D, device=dev).to(bf)
+        w, b = torch.rand(D, device=dev) + 0.5, torch.zeros(D, device=dev)
+        dy = torch.randn(rows, D, device=dev).to(bf)
+        E = rows * D
+        _, rstd = _C.rms_norm_fwd(x, w, 1e-6)
+        rec(f"rmsnorm fwd bf16 [{rows},{D}]", timeit(lambda: _C.rms_norm_fwd(x, w, 1e-6), iters), E * 4)
+        rec(f"rmsnorm bwd bf16 [{rows},{D}]", timeit(lambda: _C.rms_norm_bwd(dy, x, w, rstd), iters), E * 6)
+        _, mu, rs = _C.layer_norm_fwd(x, w, b, 1e-5, bf)
+        rec(f"layernorm fwd bf16 [{rows},{D}] (yardstick)", timeit(lambda: _C.layer_norm_fwd(x, w, b, 1e-5, bf), iters),
+            E * 4)
+        rec(f"layernorm bwd bf16 [{rows},{D}] (yardstick)",
+            timeit(lambda: _C.layer_norm_bwd(dy, x, w, b, mu, rs), iters), E * 6)
+        rec(f"stock rmsnorm fwd bf16 [{rows},{D}]", timeit(lambda: stock_rms(x, w), iters), E * 4)
+        xr, wr = x.clone().requires_grad_(), w.clone().requires_grad_()
+
+        def stock_fb():
+            xr.grad = wr.grad = None
+            stock_rms(xr, wr).backward(dy)
+
+        rec(f"stock rmsnorm fwd+bwd bf16 [{rows},{D}]", timeit(stock_fb, iters), E * 10)
+
+    B, T, C3, H = 8, 1024, 2304, 12
+    table = rope_table(T, 10000.0, dev)
+    qkv = torch.randn(B, T, C3, device=dev).to(bf)
+    nb = qkv.numel() * 2
+    rec(f"rope in place [{B},{T},{C3}]", timeit(lambda: _C.rope_qkv(qkv, H, table, False, True), iters), nb * 4 // 3)
+    rec(f"rope out of place (the backward) [{B},{T},{C3}]",
+        timeit(lambda: _C.rope_qkv(qkv, H, table, True, False), iters), nb * 2)
+    rec(f"stock rope [{B},{T},{C3}]", timeit(lambda: rope_qkv_reference(qkv, H, table), iters), nb * 4 // 3)
+
+    M, Fh = 8192, 2048
+    p = torch.randn(M, 2 * Fh, device=dev).to(bf)
+    dy = torch.randn(M, Fh, device=dev).to(bf)
+    rec(f"swiglu fwd [{M},2*{Fh}]", timeit(lambda: _C.swiglu_fwd(p), iters), M * Fh * 6)
+    rec(f"swiglu bwd [{M},2*{Fh}]", timeit(lambda: _C.swiglu_bwd(dy, p), iters), M * Fh * 10)
+
+    def stock_swiglu(t):
+        g, u = t.chunk(2, -1)
+        return F.silu(g) * u
+
+    rec(f"stock swiglu fwd [{M},2*{Fh}]", timeit(lambda: stock_swiglu(p), iters), M * Fh * 6)
+    pr = p.clone().requires_grad_()
+
+    def stock_swiglu_fb():
+        pr.grad = None
+        stock_swiglu(pr).backward(dy)
+
+    rec(f"stock swiglu fwd+bwd [{M},2*{Fh}]", timeit(stock_swiglu_fb, iters), M * Fh * 16)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--only", default=None, choices=["llama"], help="run one section only")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     bf = torch.bfloat16
@@ -49,6 +116,13 @@ def main():
              "TB_per_s": round(nbytes / (ms * 1e-3) / 1e12, 2)}
         res.append(r)
         print(json.dumps(r), flush=True)
+
+    if a.only == "llama":
+        llama_ops(rec, a.iters, dev)
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(res, f, indent=1)
+        return
 
     cl = torch.channels_last
     for (n, c, h, w, resid) in [(256, 64, 56, 56, False), (256, 256, 56, 56, True), (256, 128, 28, 28, False),
@@ -178,6 +252,7 @@ def main():
             rec(f"fused {label} op {tag}", timeit(fn, a.iters), nel * 4 * words)
         for label, words, opt in opts:
             rec(f"fused {label} step {tag}", timeit(lambda: opt.step(), a.iters), nel * 4 * words)
+    llama_ops(rec, a.iters, dev)
     if a.json:
         with open(a.json, "w") as f:
             json.dump(res, f, indent=1)

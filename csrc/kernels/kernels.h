@@ -30,21 +30,29 @@ struct TableView {
 void mt_copy(TableView t, int64_t nchunks, DType src, DType dst, float scale, hipStream_t s);
 
 // Fused SGD (torch.optim.SGD semantics). lists: 0 param, 1 grad, 2 momentum buffer (optional).
-void mt_sgd(TableView t, int64_t nchunks, DType p, float lr, float momentum, float dampening, float wd,
-            bool nesterov, bool maximize, bool first_step, bool has_buf, float grad_scale, hipStream_t s);
+// The complements (one_minus_dampening here, one_minus_beta1 / one_minus_beta2 /
+// one_minus_rho below) are computed in double by the caller and rounded once,
+// as LambParams::omb1 / omb2: the kernels never form 1.f - x.
+void mt_sgd(TableView t, int64_t nchunks, DType p, float lr, float momentum, float dampening,
+            float one_minus_dampening, float wd, bool nesterov, bool maximize, bool first_step, bool has_buf,
+            float grad_scale, hipStream_t s);
 
 // Fused Adam / AdamW. lists: 0 param, 1 grad, 2 exp_avg, 3 exp_avg_sq, 4 max_exp_avg_sq (amsgrad),
 // then (shadow) a bf16 copy of the updated parameter.
-void mt_adam(TableView t, int64_t nchunks, DType p, float lr, float beta1, float beta2, float eps, float wd,
-             float bias_c1, float bias_c2_sqrt, bool amsgrad, bool decoupled_wd, bool maximize, float grad_scale,
-             bool shadow, int step_list, hipStream_t s);
+void mt_adam(TableView t, int64_t nchunks, DType p, float lr, float beta1, float beta2, float one_minus_beta1,
+             float one_minus_beta2, float eps, float wd, float bias_c1, float bias_c2_sqrt, bool amsgrad,
+             bool decoupled_wd, bool maximize, float grad_scale, bool shadow, int step_list, hipStream_t s);
 
 // Fused Adadelta. lists: 0 param, 1 grad, 2 square_avg, 3 acc_delta.
-void mt_adadelta(TableView t, int64_t nchunks, DType p, float lr, float rho, float eps, float wd, bool maximize,
-                 float grad_scale, hipStream_t s);
+void mt_adadelta(TableView t, int64_t nchunks, DType p, float lr, float rho, float one_minus_rho, float eps, float wd,
+                 bool maximize, float grad_scale, hipStream_t s);
 
 // Sum of squares per tensor list -> out[0] (fp32, accumulated with atomics
 // per workgroup) and non-finite flag out[1]. list 0 = tensors.
+// out[1] tests the ELEMENTS, not the sum: it is set to 1 when any element is
+// inf or NaN and stays 0 on finite input even where the squares overflow
+// (x = 1e30 gives out[0] = inf, out[1] = 0). A caller that must not use an
+// overflowed norm checks isfinite(out[0]) as well.
 void mt_sumsq(TableView t, int64_t nchunks, DType d, float* out, hipStream_t s);
 // embedding.hip: gw[V][D] += per-index sums of g [M][D] (fp32; V <= 8, D % 4 == 0)
 bool emb_small_supported(int64_t V, int64_t D);

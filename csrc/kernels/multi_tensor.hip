@@ -81,7 +81,14 @@ struct Acc<F16> {
   using S = __half;
   static constexpr int kVecBytes = 8;
   __device__ static float ld(const void* p, int64_t i) { return __half2float(static_cast<const __half*>(p)[i]); }
-  __device__ static void st(void* p, int64_t i, float v) { static_cast<__half*>(p)[i] = __float2half(v); }
+  // The value gets a register of its own before the conversion: hipcc otherwise
+  // folds a multiply in front of it into v_fma_mixlo_f16(a, b, +0), and
+  // (-0) + (+0) = +0 loses the sign of a zero product (mt_copy of -0.0).
+  __device__ static __half cvt(float v) {
+    asm volatile("" : "+v"(v));
+    return __float2half(v);
+  }
+  __device__ static void st(void* p, int64_t i, float v) { static_cast<__half*>(p)[i] = cvt(v); }
   __device__ static void ld4(const void* p, int64_t i, float (&o)[4]) {
     const __half* h = static_cast<const __half*>(p) + i;
     const uint2 v = *reinterpret_cast<const uint2*>(h);
@@ -93,7 +100,7 @@ struct Acc<F16> {
     uint2 v;
     __half* hv = reinterpret_cast<__half*>(&v);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) hv[k] = __float2half(o[k]);
+    for (int k = 0; k < 4; ++k) hv[k] = cvt(o[k]);
     *reinterpret_cast<uint2*>(static_cast<__half*>(p) + i) = v;
   }
 };
@@ -182,6 +189,7 @@ __global__ void __launch_bounds__(kThreads) mt_rawcopy_kernel(Tab tab, int64_t n
 // ------------------------------------------------------------------- SGD ---
 struct SgdArgs {
   float lr, momentum, dampening, wd, grad_scale;
+  float omd;  // 1 - dampening, rounded from double (as LambParams::omb1)
   bool nesterov, maximize, first_step, has_buf;
 };
 
@@ -191,7 +199,7 @@ __device__ __forceinline__ void sgd_elem(float& p, float g_raw, float* b, const 
   if (a.maximize) g = -g;
   if (a.wd != 0.f) g = fmaf(a.wd, p, g);
   if (a.has_buf) {
-    const float nb = a.first_step ? g : fmaf(a.momentum, *b, (1.f - a.dampening) * g);
+    const float nb = a.first_step ? g : fmaf(a.momentum, *b, a.omd * g);
     *b = nb;
     g = a.nesterov ? fmaf(a.momentum, nb, g) : nb;
   }
@@ -240,6 +248,9 @@ __global__ void __launch_bounds__(kThreads) mt_sgd_kernel(Tab tab, int64_t nchun
 // ------------------------------------------------------------------ Adam ---
 struct AdamArgs {
   float lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, grad_scale;
+  // 1 - beta rounded from double: 1.f - 0.999f is 1.3e-5 relative below
+  // float(0.001), which scaled every exp_avg_sq increment by that much
+  float omb1, omb2;
   bool amsgrad, decoupled, maximize, shadow;
   // >= 0: table list holding one device fp32 `step` scalar per tensor
   // (capturable mode: bias corrections derived on device, so a replayed HIP
@@ -254,8 +265,8 @@ __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v,
     if (a.decoupled) p *= (1.f - a.lr * a.wd);
     else g = fmaf(a.wd, p, g);
   }
-  m = fmaf(1.f - a.beta1, g - m, m);  // lerp(m, g, 1-beta1)
-  v = fmaf(a.beta2, v, (1.f - a.beta2) * g * g);
+  m = fmaf(a.omb1, g - m, m);  // lerp(m, g, 1-beta1)
+  v = fmaf(a.beta2, v, a.omb2 * g * g);
   float denom;
   if (a.amsgrad) {
     vmax = fmaxf(vmax, v);
@@ -330,6 +341,7 @@ __global__ void __launch_bounds__(kThreads) mt_adam_kernel(Tab tab, int64_t nchu
 // -------------------------------------------------------------- Adadelta ---
 struct AdadeltaArgs {
   float lr, rho, eps, wd, grad_scale;
+  float omr;  // 1 - rho, rounded from double
   bool maximize;
 };
 
@@ -337,10 +349,10 @@ __device__ __forceinline__ void adadelta_elem(float& p, float g, float& sq, floa
   g *= a.grad_scale;
   if (a.maximize) g = -g;
   if (a.wd != 0.f) g = fmaf(a.wd, p, g);
-  sq = fmaf(a.rho, sq, (1.f - a.rho) * g * g);
+  sq = fmaf(a.rho, sq, a.omr * g * g);
   const float stdv = sqrtf(sq + a.eps);
   const float delta = sqrtf(acc + a.eps) / stdv * g;
-  acc = fmaf(a.rho, acc, (1.f - a.rho) * delta * delta);
+  acc = fmaf(a.rho, acc, a.omr * delta * delta);
   p = fmaf(-a.lr, delta, p);
 }
 
@@ -783,28 +795,29 @@ void mt_copy(TableView t, int64_t nchunks, DType src, DType dst, float scale, hi
       hipLaunchKernelGGL((mt_copy_kernel<SD, DD>), grid_for(nchunks), dim3(kThreads), 0, s, tab_of(t), nchunks, scale)));
 }
 
-void mt_sgd(TableView t, int64_t nchunks, DType p, float lr, float momentum, float dampening, float wd,
-            bool nesterov, bool maximize, bool first_step, bool has_buf, float grad_scale, hipStream_t s) {
+void mt_sgd(TableView t, int64_t nchunks, DType p, float lr, float momentum, float dampening,
+            float one_minus_dampening, float wd, bool nesterov, bool maximize, bool first_step, bool has_buf,
+            float grad_scale, hipStream_t s) {
   if (nchunks <= 0) return;
-  SgdArgs a{lr, momentum, dampening, wd, grad_scale, nesterov, maximize, first_step, has_buf};
+  SgdArgs a{lr, momentum, dampening, wd, grad_scale, one_minus_dampening, nesterov, maximize, first_step, has_buf};
   DK_DISPATCH_DTYPE(p, PD,
       hipLaunchKernelGGL((mt_sgd_kernel<PD>), grid_for(nchunks), dim3(kThreads), 0, s, tab_of(t), nchunks, a));
 }
 
-void mt_adam(TableView t, int64_t nchunks, DType p, float lr, float beta1, float beta2, float eps, float wd,
-             float bias_c1, float bias_c2_sqrt, bool amsgrad, bool decoupled_wd, bool maximize, float grad_scale,
-             bool shadow, int step_list, hipStream_t s) {
+void mt_adam(TableView t, int64_t nchunks, DType p, float lr, float beta1, float beta2, float one_minus_beta1,
+             float one_minus_beta2, float eps, float wd, float bias_c1, float bias_c2_sqrt, bool amsgrad,
+             bool decoupled_wd, bool maximize, float grad_scale, bool shadow, int step_list, hipStream_t s) {
   if (nchunks <= 0) return;
-  AdamArgs a{lr, beta1, beta2, eps, wd, bias_c1, bias_c2_sqrt, grad_scale, amsgrad, decoupled_wd, maximize, shadow,
-             step_list};
+  AdamArgs a{lr, beta1, beta2, eps, wd, bias_c1, bias_c2_sqrt, grad_scale, one_minus_beta1, one_minus_beta2,
+             amsgrad, decoupled_wd, maximize, shadow, step_list};
   DK_DISPATCH_DTYPE(p, PD,
       hipLaunchKernelGGL((mt_adam_kernel<PD>), grid_for(nchunks), dim3(kThreads), 0, s, tab_of(t), nchunks, a));
 }
 
-void mt_adadelta(TableView t, int64_t nchunks, DType p, float lr, float rho, float eps, float wd, bool maximize,
-                 float grad_scale, hipStream_t s) {
+void mt_adadelta(TableView t, int64_t nchunks, DType p, float lr, float rho, float one_minus_rho, float eps, float wd,
+                 bool maximize, float grad_scale, hipStream_t s) {
   if (nchunks <= 0) return;
-  AdadeltaArgs a{lr, rho, eps, wd, grad_scale, maximize};
+  AdadeltaArgs a{lr, rho, eps, wd, grad_scale, one_minus_rho, maximize};
   DK_DISPATCH_DTYPE(p, PD,
       hipLaunchKernelGGL((mt_adadelta_kernel<PD>), grid_for(nchunks), dim3(kThreads), 0, s, tab_of(t), nchunks, a));
 }

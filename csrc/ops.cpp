@@ -164,6 +164,14 @@ void check_lists(const std::vector<const TensorList*>& lists, const char* what) 
   }
 }
 
+// The kernels (and the CPU loops) read every list at the element size of
+// params[0]: a narrower tensor anywhere would be read past its end.
+void check_same_dtype(const std::vector<const TensorList*>& lists, const char* what) {
+  const auto dt = (*lists[0])[0].scalar_type();
+  for (auto* l : lists)
+    for (auto& t : *l) DK_CHECK(t.scalar_type() == dt, what, ": one dtype per call (parameters, gradients and state)");
+}
+
 bool on_gpu(const TensorList& l) { return !l.empty() && l[0].is_cuda(); }
 
 hipStream_t cur_stream(const at::Tensor& t) {
@@ -203,7 +211,9 @@ void mt_copy(const TensorList& src, const TensorList& dst, double scale) {
       // raw memory-order copy (layouts agree)
       dst[i].as_strided({dst[i].numel()}, {1}).copy_(src[i].as_strided({src[i].numel()}, {1}));
     } else {
-      dst[i].as_strided({dst[i].numel()}, {1}).copy_(src[i].as_strided({src[i].numel()}, {1}).mul(scale));
+      // product in fp32 as in the kernel: a 16-bit src.mul(scale) would round to the source dtype first
+      dst[i].as_strided({dst[i].numel()}, {1}).copy_(
+          src[i].as_strided({src[i].numel()}, {1}).to(at::kFloat).mul(static_cast<float>(scale)));
     }
   }
 }
@@ -217,11 +227,14 @@ void fused_sgd(const TensorList& params, const TensorList& grads, const TensorLi
   std::vector<const TensorList*> lists{&params, &grads};
   if (has_buf) lists.push_back(&bufs);
   check_lists(lists, "fused_sgd");
+  check_same_dtype(lists, "fused_sgd");
+  // 1 - dampening in double, rounded once (1.f - float(d) is not float(1 - d))
+  const float omd = static_cast<float>(1.0 - dampening);
   if (on_gpu(params)) {
     c10::hip::HIPGuard guard(params[0].device().index());
     auto tab = get_table(lists);
     kern::mt_sgd(kern::TableView{tab.dev.data_ptr<int64_t>(), tab.n}, tab.nchunks, kdtype(params[0].scalar_type()),
-                 static_cast<float>(lr), static_cast<float>(momentum), static_cast<float>(dampening),
+                 static_cast<float>(lr), static_cast<float>(momentum), static_cast<float>(dampening), omd,
                  static_cast<float>(weight_decay), nesterov, maximize, first_step, has_buf,
                  static_cast<float>(grad_scale), cur_stream(params[0]));
     return;
@@ -240,7 +253,7 @@ void fused_sgd(const TensorList& params, const TensorList& grads, const TensorLi
           if (has_buf) {
             float bv = first_step ? gv
                                   : static_cast<float>(momentum) * static_cast<float>(b[i]) +
-                                        (1.f - static_cast<float>(dampening)) * gv;
+                                        omd * gv;
             b[i] = static_cast<scalar_t>(bv);
             gv = nesterov ? gv + static_cast<float>(momentum) * bv : bv;
           }
@@ -269,6 +282,11 @@ void fused_adam(const TensorList& params, const TensorList& grads, const TensorL
                 "fused_adam: shadows must be contiguous bf16 copies of contiguous fp32 params");
   }
   check_lists(lists, "fused_adam");
+  {
+    std::vector<const TensorList*> typed{&params, &grads, &exp_avgs, &exp_avg_sqs};
+    if (amsgrad) typed.push_back(&max_exp_avg_sqs);
+    check_same_dtype(typed, "fused_adam");
+  }
   // capturable mode: one device fp32 step scalar per tensor (already
   // incremented by the caller), appended as an extra table list (the table
   // sizes chunks by list 0 only, so 1-element rows are fine there)
@@ -283,11 +301,13 @@ void fused_adam(const TensorList& params, const TensorList& grads, const TensorL
   }
   const double bc1 = 1.0 - std::pow(beta1, step);
   const double bc2_sqrt = std::sqrt(1.0 - std::pow(beta2, step));
+  // 1 - beta in double, rounded once: 1.f - 0.999f is 1.3e-5 below float(0.001)
+  const float omb1 = static_cast<float>(1.0 - beta1), omb2 = static_cast<float>(1.0 - beta2);
   if (on_gpu(params)) {
     c10::hip::HIPGuard guard(params[0].device().index());
     auto tab = get_table(lists);
     kern::mt_adam(kern::TableView{tab.dev.data_ptr<int64_t>(), tab.n}, tab.nchunks, kdtype(params[0].scalar_type()),
-                  static_cast<float>(lr), static_cast<float>(beta1), static_cast<float>(beta2),
+                  static_cast<float>(lr), static_cast<float>(beta1), static_cast<float>(beta2), omb1, omb2,
                   static_cast<float>(eps), static_cast<float>(weight_decay), static_cast<float>(bc1),
                   static_cast<float>(bc2_sqrt), amsgrad, decoupled, maximize, static_cast<float>(grad_scale),
                   shadow, step_list, cur_stream(params[0]));
@@ -300,7 +320,7 @@ void fused_adam(const TensorList& params, const TensorList& grads, const TensorL
       scalar_t* m = P<scalar_t>(exp_avgs[t]);
       scalar_t* v = P<scalar_t>(exp_avg_sqs[t]);
       scalar_t* vm = amsgrad ? P<scalar_t>(max_exp_avg_sqs[t]) : nullptr;
-      const float flr = static_cast<float>(lr), b1 = static_cast<float>(beta1), b2 = static_cast<float>(beta2);
+      const float flr = static_cast<float>(lr), b2 = static_cast<float>(beta2);
       const float feps = static_cast<float>(eps), wd = static_cast<float>(weight_decay);
       at::parallel_for(0, params[t].numel(), 16384, [&](int64_t s, int64_t e) {
         for (int64_t i = s; i < e; ++i) {
@@ -313,8 +333,8 @@ void fused_adam(const TensorList& params, const TensorList& grads, const TensorL
           }
           float mv = static_cast<float>(m[i]);
           float vv = static_cast<float>(v[i]);
-          mv = mv + (1.f - b1) * (gv - mv);
-          vv = b2 * vv + (1.f - b2) * gv * gv;
+          mv = mv + omb1 * (gv - mv);
+          vv = b2 * vv + omb2 * gv * gv;
           float denom;
           if (amsgrad) {
             float mx = std::max(static_cast<float>(vm[i]), vv);
@@ -341,11 +361,13 @@ void fused_adadelta(const TensorList& params, const TensorList& grads, const Ten
   if (params.empty()) return;
   std::vector<const TensorList*> lists{&params, &grads, &square_avgs, &acc_deltas};
   check_lists(lists, "fused_adadelta");
+  check_same_dtype(lists, "fused_adadelta");
+  const float omr = static_cast<float>(1.0 - rho);  // in double, rounded once
   if (on_gpu(params)) {
     c10::hip::HIPGuard guard(params[0].device().index());
     auto tab = get_table(lists);
     kern::mt_adadelta(kern::TableView{tab.dev.data_ptr<int64_t>(), tab.n}, tab.nchunks,
-                      kdtype(params[0].scalar_type()), static_cast<float>(lr), static_cast<float>(rho),
+                      kdtype(params[0].scalar_type()), static_cast<float>(lr), static_cast<float>(rho), omr,
                       static_cast<float>(eps), static_cast<float>(weight_decay), maximize,
                       static_cast<float>(grad_scale), cur_stream(params[0]));
     return;
@@ -363,10 +385,10 @@ void fused_adadelta(const TensorList& params, const TensorList& grads, const Ten
           float gv = static_cast<float>(g[i]) * static_cast<float>(grad_scale);
           if (maximize) gv = -gv;
           if (weight_decay != 0.0) gv += static_cast<float>(weight_decay) * pv;
-          float s2 = r * static_cast<float>(sq[i]) + (1.f - r) * gv * gv;
+          float s2 = r * static_cast<float>(sq[i]) + omr * gv * gv;
           float stdv = std::sqrt(s2 + e);
           float delta = std::sqrt(static_cast<float>(ac[i]) + e) / stdv * gv;
-          float a2 = r * static_cast<float>(ac[i]) + (1.f - r) * delta * delta;
+          float a2 = r * static_cast<float>(ac[i]) + omr * delta * delta;
           sq[i] = static_cast<scalar_t>(s2);
           ac[i] = static_cast<scalar_t>(a2);
           p[i] = static_cast<scalar_t>(pv - static_cast<float>(lr) * delta);
@@ -391,12 +413,6 @@ at::Tensor ratio_slots(const TensorList& params, TensorList& slots) {
   slots.reserve(n);
   for (int64_t i = 0; i < n; ++i) slots.push_back(ratio.narrow(0, i, 1));
   return ratio;
-}
-
-void check_same_dtype(const std::vector<const TensorList*>& lists, const char* what) {
-  const auto dt = (*lists[0])[0].scalar_type();
-  for (auto* l : lists)
-    for (auto& t : *l) DK_CHECK(t.scalar_type() == dt, what, ": one dtype per call (parameters, gradients and state)");
 }
 
 int64_t chunks_of(int64_t n) { return (n + kern::kChunk - 1) / kern::kChunk; }
@@ -626,8 +642,10 @@ at::Tensor sumsq(const TensorList& tensors) {
     bad = bad || !f.isfinite().all().item<bool>();
   }
   at::Tensor out = at::zeros({2}, at::kFloat);
-  out[0] = acc;
-  out[1] = bad ? 1.0 : 0.0;
+  // as the kernel's fp32 sum: a sum beyond FLT_MAX is inf (`out[0] = acc`
+  // threw "cannot be converted to type float without overflow" instead)
+  out.data_ptr<float>()[0] = static_cast<float>(acc);
+  out.data_ptr<float>()[1] = bad ? 1.f : 0.f;
   return out;
 }
 

@@ -17,14 +17,15 @@ namespace {
 }  // namespace
 
 void mt_copy(TableView, int64_t, DType, DType, float, hipStream_t) { gpu_only("mt_copy"); }
-void mt_sgd(TableView, int64_t, DType, float, float, float, float, bool, bool, bool, bool, float, hipStream_t) {
+void mt_sgd(TableView, int64_t, DType, float, float, float, float, float, bool, bool, bool, bool, float,
+            hipStream_t) {
   gpu_only("mt_sgd");
 }
-void mt_adam(TableView, int64_t, DType, float, float, float, float, float, float, float, bool, bool, bool, float, bool,
-             int, hipStream_t) {
+void mt_adam(TableView, int64_t, DType, float, float, float, float, float, float, float, float, float, bool, bool, bool,
+             float, bool, int, hipStream_t) {
   gpu_only("mt_adam");
 }
-void mt_adadelta(TableView, int64_t, DType, float, float, float, float, bool, float, hipStream_t) {
+void mt_adadelta(TableView, int64_t, DType, float, float, float, float, float, bool, float, hipStream_t) {
   gpu_only("mt_adadelta");
 }
 void mt_sumsq(TableView, int64_t, DType, float*, hipStream_t) { gpu_only("mt_sumsq"); }

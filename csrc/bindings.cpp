@@ -19,6 +19,9 @@ void bind(pybind11::module& m);
 namespace llama {
 void bind(pybind11::module& m);
 }
+namespace augment {
+void bind(pybind11::module& m);
+}
 }  // namespace dcp
 #include "trace/trace.h"
 #include "store/tcp_store.h"
@@ -263,4 +266,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   stem::bind(m);
   convnet::bind(m);
   llama::bind(m);
+  augment::bind(m);
 }

@@ -22,6 +22,9 @@ void bind(pybind11::module& m);
 namespace augment {
 void bind(pybind11::module& m);
 }
+namespace attn128 {
+void bind(pybind11::module& m);
+}
 }  // namespace dcp
 #include "trace/trace.h"
 #include "store/tcp_store.h"
@@ -267,4 +270,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   convnet::bind(m);
   llama::bind(m);
   augment::bind(m);
+  attn128::bind(m);
 }

@@ -78,5 +78,27 @@ void attn_fwd(const AttnParams& p, AttnTensor q, AttnTensor k, AttnTensor v, Att
 void attn_bwd(const AttnParams& p, AttnTensor q, AttnTensor k, AttnTensor v, AttnTensor o, AttnTensor dout,
               const float* lse, float* delta, AttnOut dq, AttnOut dk, AttnOut dv, hipStream_t s);
 
+// ---- head dim 128 (attention_d128.hip) ------------------------------------
+// The same tensor views with 128 channels per head ([B, T, H*128]); softmax
+// scale 1/sqrt(128); causal or not; no dropout, no key-padding mask.
+struct Attn128Params {
+  int B, H, T;
+  bool causal;
+};
+
+// T a multiple of 64, at most 8192
+bool attn128_supported(int T);
+
+// o [B, T, H*128] (strided), lse [B*H, T] fp32 (log2 domain, internal to the backward)
+void attn128_fwd(const Attn128Params& p, AttnTensor q, AttnTensor k, AttnTensor v, AttnOut o, float* lse,
+                 hipStream_t s);
+
+// delta [B*H, T] fp32 workspace (written by the dQ kernel, read by dK/dV);
+// dq/dk/dv strided outputs. Returns the first launch error (the dK/dV kernel
+// asks for more than 64 KiB of LDS).
+hipError_t attn128_bwd(const Attn128Params& p, AttnTensor q, AttnTensor k, AttnTensor v, AttnTensor o,
+                       AttnTensor dout, const float* lse, float* delta, AttnOut dq, AttnOut dk, AttnOut dv,
+                       hipStream_t s);
+
 }  // namespace kern
 }  // namespace dcp

@@ -28,13 +28,14 @@ void rms_backward(int xdtype, int ydtype, const void* dy, const void* x, const f
                   float* dw, float* part, int64_t rows, int D, bool accum, hipStream_t s,
                   const void* gres = nullptr);
 
-// ---- rotary embedding on packed [rows = B·T, 3·heads·64] bf16 -------------
-// Rotate-half pairs (i, i + 32) of every q and k head by the angle of table
-// row (row % T); table: fp32 [T_max, 64] = cos[32] | sin[32] per position.
+// ---- rotary embedding on packed [rows = B·T, 3·heads·2·half] bf16 ---------
+// Rotate-half pairs (i, i + half) of every q and k head by the angle of table
+// row (row % T); table: fp32 [T_max, 2·half] = cos[half] | sin[half] per
+// position; half = 32 (head dim 64) or 64 (head dim 128).
 // out == in: in place (v is not touched); else v is copied through.
 // inverse: rotate by −θ (the backward).
 void rope_qkv(const void* in, void* out, const float* table, int64_t rows, int T, int heads, bool inverse,
-              hipStream_t s);
+              hipStream_t s, int half = 32);
 
 // ---- SwiGLU on packed [M, 2F] bf16 (gate | up), F % 8 == 0 ----------------
 // y[M, F] = silu(gate) · up

@@ -1,21 +1,22 @@
-// Rotary position embedding on the packed qkv projection [B·T, 3·H·64] bf16
+// Rotary position embedding on the packed qkv projection [B·T, 3·H·D] bf16
 // that feeds flash_attn_qkv: the q and k thirds are rotated, head by head,
-// in the rotate-half pairing (i, i + 32); v is left alone.
+// in the rotate-half pairing (i, i + h), h = D / 2 (the kernel is templated on
+// h: 32 for head dim 64, 64 for head dim 128); v is left alone.
 //
-//   y_i      = x_i · cos θ − x_{i+32} · sin θ
-//   y_{i+32} = x_{i+32} · cos θ + x_i · sin θ        θ = θ(t, i), t = row % T
+//   y_i     = x_i · cos θ − x_{i+h} · sin θ
+//   y_{i+h} = x_{i+h} · cos θ + x_i · sin θ          θ = θ(t, i), t = row % T
 //
-// cos / sin come from an fp32 table [T_max, 2, 32] (cos row | sin row per
+// cos / sin come from an fp32 table [T_max, 2, h] (cos row | sin row per
 // position), the arithmetic is fp32 and the result is rounded to bf16 once.
 // The backward is the same kernel with the sign of sin flipped (a rotation by
 // −θ of the incoming gradient): nothing is saved by the forward.
 //
 // Work item = one 16-B vector of a head's first half together with its
-// partner 32 elements on: 4 items per head, 8·H per row (q and k are
-// adjacent: columns [0, 2·H·64)). Four consecutive lanes read two contiguous
-// 64-B runs, so a wave covers 16 whole heads. In place (out == in) only those
-// 2/3 of the bytes move each way; out of place the v third is copied through
-// by 8·H more items per row.
+// partner h elements on: h/8 items per head (4 / 8), h/4·H per row (q and k
+// are adjacent: columns [0, 2·H·D)). h/8 consecutive lanes read two contiguous
+// 2h-B runs, so a wave covers 16 / 8 whole heads. In place (out == in) only
+// those 2/3 of the bytes move each way; out of place the v third is copied
+// through by h/4·H more items per row.
 #include <hip/hip_runtime.h>
 
 #include "bf16_vec.h"
@@ -45,32 +46,34 @@ __device__ __forceinline__ float diff_of_products(float a, float c, float b, flo
   return fmaf(a, c, -w) + e;
 }
 
-// ipr = items per row: 8·H (in place) or 16·H (the second 8·H copy v).
+// ipr = items per row: HALF/4·H (in place) or HALF/2·H (the second half copy v).
 // in / out may be the same buffer (no __restrict__): an item reads its 32
 // bytes before it writes them and no other item touches them.
-template <bool COPY_V>
+template <int HALF, bool COPY_V>
 __global__ void __launch_bounds__(kT) rope_qkv_kernel(const uint16_t* in, uint16_t* out,
                                                       const float* __restrict__ table, int64_t items, int T, int H,
                                                       float sgn) {
   const int64_t it = static_cast<int64_t>(blockIdx.x) * kT + threadIdx.x;
   if (it >= items) return;
-  const int ipr = (COPY_V ? 16 : 8) * H;
+  constexpr int IPH = HALF / 8, D = 2 * HALF;  // items per head, head dim
+  const int rot = 2 * IPH * H;                 // rotating items per row (q and k)
+  const int ipr = (COPY_V ? 2 : 1) * rot;
   const int64_t row = it / ipr;
   const int i = static_cast<int>(it - row * ipr);
-  const int64_t base = row * (3 * 64 * static_cast<int64_t>(H));
-  if (COPY_V && i >= 8 * H) {
-    const int64_t o = base + 2 * 64 * static_cast<int64_t>(H) + (i - 8 * H) * 8;
+  const int64_t base = row * (3 * D * static_cast<int64_t>(H));
+  if (COPY_V && i >= rot) {
+    const int64_t o = base + 2 * D * static_cast<int64_t>(H) + (i - rot) * 8;
     *reinterpret_cast<uint4*>(out + o) = *reinterpret_cast<const uint4*>(in + o);
     return;
   }
-  const int head = i >> 2, j = i & 3;  // head over q then k; j: which 8 of the 32 pairs
-  const int64_t o = base + head * 64 + j * 8;
+  const int head = i / IPH, j = i % IPH;  // head over q then k; j: which 8 of the HALF pairs
+  const int64_t o = base + head * D + j * 8;
   const uint4 a = *reinterpret_cast<const uint4*>(in + o);
-  const uint4 b = *reinterpret_cast<const uint4*>(in + o + 32);
-  const float* tr = table + static_cast<int64_t>(row % T) * 64 + j * 8;
+  const uint4 b = *reinterpret_cast<const uint4*>(in + o + HALF);
+  const float* tr = table + static_cast<int64_t>(row % T) * D + j * 8;
   float c[8], s[8];
   ld8f(tr, c);
-  ld8f(tr + 32, s);
+  ld8f(tr + HALF, s);
   const uint32_t aw[4] = {a.x, a.y, a.z, a.w}, bw[4] = {b.x, b.y, b.z, b.w};
   uint32_t ya[4], yb[4];
 #pragma unroll
@@ -81,22 +84,30 @@ __global__ void __launch_bounds__(kT) rope_qkv_kernel(const uint16_t* in, uint16
     yb[k] = pack2(diff_of_products(b0, c[2 * k], a0, -s0), diff_of_products(b1, c[2 * k + 1], a1, -s1));
   }
   *reinterpret_cast<uint4*>(out + o) = make_uint4(ya[0], ya[1], ya[2], ya[3]);
-  *reinterpret_cast<uint4*>(out + o + 32) = make_uint4(yb[0], yb[1], yb[2], yb[3]);
+  *reinterpret_cast<uint4*>(out + o + HALF) = make_uint4(yb[0], yb[1], yb[2], yb[3]);
 }
 
 }  // namespace
 
 void rope_qkv(const void* in, void* out, const float* table, int64_t rows, int T, int heads, bool inverse,
-              hipStream_t s) {
+              hipStream_t s, int half) {
   const bool copy_v = in != out;
-  const int64_t items = rows * (copy_v ? 16 : 8) * heads;
+  const int64_t items = rows * (copy_v ? 2 : 1) * (half / 4) * heads;
   if (items == 0) return;
   const dim3 grid(static_cast<unsigned>((items + kT - 1) / kT));
   const auto* i = static_cast<const uint16_t*>(in);
   auto* o = static_cast<uint16_t*>(out);
   const float sgn = inverse ? -1.f : 1.f;
-  if (copy_v) hipLaunchKernelGGL(rope_qkv_kernel<true>, grid, dim3(kT), 0, s, i, o, table, items, T, heads, sgn);
-  else hipLaunchKernelGGL(rope_qkv_kernel<false>, grid, dim3(kT), 0, s, i, o, table, items, T, heads, sgn);
+#define DK_ROPE(HALF, CV) \
+  hipLaunchKernelGGL((rope_qkv_kernel<HALF, CV>), grid, dim3(kT), 0, s, i, o, table, items, T, heads, sgn)
+  if (half == 64) {
+    if (copy_v) DK_ROPE(64, true);
+    else DK_ROPE(64, false);
+  } else {
+    if (copy_v) DK_ROPE(32, true);
+    else DK_ROPE(32, false);
+  }
+#undef DK_ROPE
 }
 
 }  // namespace kern

@@ -110,27 +110,28 @@ std::vector<at::Tensor> rms_norm_bwd(const at::Tensor& dy, const at::Tensor& x, 
   return {dx, accum ? at::Tensor() : dw};
 }
 
-// qkv: contiguous bf16 [B, T, 3·heads·64]; table: fp32 [T_max, 2, 32] (cos |
-// sin per position), T <= T_max. inplace: rotate qkv itself and return it;
+// qkv: contiguous bf16 [B, T, 3·heads·D]; table: fp32 [T_max, 2, D/2] (cos |
+// sin per position; its last dim sets the head dim D = 64 or 128), T <= T_max. inplace: rotate qkv itself and return it;
 // else a new tensor (v copied through). inverse: rotate by −θ (the backward).
 at::Tensor rope_qkv(const at::Tensor& qkv, int64_t heads, const at::Tensor& table, bool inverse, bool inplace) {
   DK_CHECK(qkv.is_cuda() && qkv.scalar_type() == at::kBFloat16 && qkv.dim() == 3 && qkv.is_contiguous() &&
                aligned16(qkv),
-           "rope_qkv: contiguous 16-B aligned bf16 [B, T, 3*heads*64] device tensor required");
-  DK_CHECK(heads > 0 && heads <= 4096 && qkv.size(2) == 3 * heads * 64, "rope_qkv: last dim must be 3*heads*64, got ",
-           qkv.size(2), " for ", heads, " heads");
-  const int64_t T = qkv.size(1);
+           "rope_qkv: contiguous 16-B aligned bf16 [B, T, 3*heads*head_dim] device tensor required");
   DK_CHECK(table.is_cuda() && table.device() == qkv.device() && table.scalar_type() == at::kFloat &&
-               table.is_contiguous() && table.dim() == 3 && table.size(1) == 2 && table.size(2) == 32 &&
-               aligned16(table),
-           "rope_qkv: table must be a contiguous fp32 [T_max, 2, 32] tensor on qkv's device");
+               table.is_contiguous() && table.dim() == 3 && table.size(1) == 2 &&
+               (table.size(2) == 32 || table.size(2) == 64) && aligned16(table),
+           "rope_qkv: table must be a contiguous fp32 [T_max, 2, 32 or 64] tensor on qkv's device");
+  const int64_t half = table.size(2);
+  DK_CHECK(heads > 0 && heads <= 4096 && qkv.size(2) == 3 * heads * 2 * half, "rope_qkv: last dim must be 3*heads*",
+           2 * half, ", got ", qkv.size(2), " for ", heads, " heads");
+  const int64_t T = qkv.size(1);
   DK_CHECK(T <= table.size(0), "rope_qkv: sequence length ", T, " exceeds the table's ", table.size(0), " rows");
   DK_CHECK(T < (int64_t(1) << 31), "rope_qkv: sequence too long");
   c10::hip::HIPGuard guard(qkv.device().index());
   at::Tensor out = inplace ? qkv : at::empty_like(qkv);
   if (qkv.numel())
     kern::rope_qkv(qkv.data_ptr(), out.data_ptr(), table.data_ptr<float>(), qkv.size(0) * T, static_cast<int>(T),
-                   static_cast<int>(heads), inverse, stream_of(qkv));
+                   static_cast<int>(heads), inverse, stream_of(qkv), static_cast<int>(half));
   return out;
 }
 
@@ -182,7 +183,7 @@ void bind(pybind11::module& m) {
   m.def("rms_norm_bwd", &rms_norm_bwd, "RMSNorm backward -> (dx, dweight)", py::arg("dy"), py::arg("x"),
         py::arg("weight"), py::arg("rstd"), py::arg("accumulate_into") = py::none(),
         py::arg("grad_residual") = py::none());
-  m.def("rope_qkv", &rope_qkv, "rotary embedding on the q / k thirds of a packed bf16 [B, T, 3*heads*64] projection",
+  m.def("rope_qkv", &rope_qkv, "rotary embedding on the q / k thirds of a packed bf16 [B, T, 3*heads*head_dim] projection",
         py::arg("qkv"), py::arg("heads"), py::arg("table"), py::arg("inverse") = false, py::arg("inplace") = false);
   m.def("swiglu_supported", &swiglu_supported);
   m.def("swiglu_fwd", &swiglu_fwd, "silu(gate) * up on a packed bf16 [..., 2F] projection", py::arg("packed"));

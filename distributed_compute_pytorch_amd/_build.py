@@ -91,6 +91,11 @@ _FILE_FLAGS = {
     # 33 of the forward's ~500 VALU instructions per key block, in a
     # VALU-bound loop); nothing in the file depends on NaN semantics
     "kernels/attention.hip": ["-fno-honor-nans"],
+    # the head-dim-128 kernels: the same fmaxf on MFMA outputs; no packed-fp32
+    # VALU forms in new code (v_pk_mul/add/fma_f32: the O rescale and the
+    # final scaling would otherwise pair up)
+    "kernels/attention_d128.hip": ["-fno-honor-nans", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "kernels/rope.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     # the LM-head GEMM's softmax-partials epilogue (EPI 7): 9 quieting v_max
     # per row of 8 logits per lane otherwise (the bf16 unpacks and DPP moves
     # are not known canonical); the file tests ±inf, never NaN

@@ -24,8 +24,14 @@ the bias-free Linears hand them a cached all-zero one (never a parameter, no
 gradient). ``fused=False`` is plain PyTorch (``scaled_dot_product_attention``,
 ``F.silu``); on the CPU both variants take that arithmetic.
 
+Heads are 64 or 128 wide (``n_embd // n_head``): each width has its own MFMA
+flash-attention kernels and rotary instantiation. The 128-wide kernels have no
+attention dropout, so a fused model with ``dropout > 0`` in training takes
+``scaled_dot_product_attention`` for the attention core at that width (the
+rest of the block stays fused).
+
 Out of scope: grouped-query attention (the attention kernels take equal q and
-k head counts), head dims other than 64, KV-cache decoding.
+k head counts), head dims other than 64 and 128, KV-cache decoding.
 """
 from __future__ import annotations
 
@@ -129,14 +135,17 @@ class Attention(nn.Module):
         C = cfg.n_embd
         self.wq, self.wk, self.wv, self.wo = lin(C, C), lin(C, C), lin(C, C), lin(C, C)
         self.n_head, self.dropout, self.fused = cfg.n_head, cfg.dropout, fused
+        self.head_dim = C // cfg.n_head
 
     def forward(self, x, table):
         B, T, C = x.shape
-        h = self.n_head
+        h, hd = self.n_head, self.head_dim
         p = self.dropout if self.training else 0.0
         if self.fused:
             qkv = _packed_bias_free(x, (self.wq, self.wk, self.wv))
-            if attn_supported(qkv[..., :C], h) and table.is_cuda and table.dtype == torch.float32:
+            # the 128-wide kernels have no dropout: that case takes the SDPA core below
+            if (attn_supported(qkv[..., :C], h, head_dim=hd) and not (hd == 128 and p > 0.0) and table.is_cuda
+                    and table.dtype == torch.float32):
                 # rotated in place on the GEMM's output, read in place by the
                 # MFMA flash attention: no head transposes, one packed gradient
                 qkv = apply_rope_qkv(qkv, h, table, inplace=True)
@@ -144,9 +153,9 @@ class Attention(nn.Module):
         else:
             qkv = torch.cat([self.wq(x), self.wk(x), self.wv(x)], -1)
         q, k, v = rope_qkv_reference(qkv, h, table).split(C, dim=2)
-        q = q.view(B, T, h, 64).transpose(1, 2)
-        k = k.view(B, T, h, 64).transpose(1, 2)
-        v = v.view(B, T, h, 64).transpose(1, 2)
+        q = q.view(B, T, h, hd).transpose(1, 2)
+        k = k.view(B, T, h, hd).transpose(1, 2)
+        v = v.view(B, T, h, hd).transpose(1, 2)
         y = F.scaled_dot_product_attention(q, k, v, dropout_p=p, is_causal=True)
         return self.wo(y.transpose(1, 2).contiguous().view(B, T, C))
 
@@ -195,9 +204,9 @@ class Block(nn.Module):
 class LlamaForCausalLM(nn.Module):
     def __init__(self, cfg: LlamaConfig = LlamaConfig(), fused: bool = True):
         super().__init__()
-        if cfg.n_embd != 64 * cfg.n_head:
-            raise ValueError(f"LlamaForCausalLM: head dim 64 required (n_embd = 64 * n_head), got n_embd "
-                             f"{cfg.n_embd} with {cfg.n_head} heads")
+        if cfg.n_head <= 0 or cfg.n_embd % cfg.n_head != 0 or cfg.n_embd // cfg.n_head not in (64, 128):
+            raise ValueError(f"LlamaForCausalLM: head dim 64 or 128 required (n_embd = 64 * n_head or "
+                             f"128 * n_head), got n_embd {cfg.n_embd} with {cfg.n_head} heads")
         self.cfg, self.fused = cfg, fused
         self.tok_embeddings = (FusedEmbedding if fused else nn.Embedding)(cfg.vocab, cfg.n_embd)
         self.drop = nn.Dropout(cfg.dropout)
@@ -206,8 +215,9 @@ class LlamaForCausalLM(nn.Module):
         # a plain module either way: the head runs through lm_head_cross_entropy
         # on the padded bf16 copy the LinearWeightPrep keeps (``heads=``)
         self.output = nn.Linear(cfg.n_embd, cfg.vocab, bias=False)
-        # cos / sin of every position, fp32 [block_size, 2, 32]; not a state_dict entry
-        self.register_buffer("rope", rope_table(cfg.block_size, cfg.rope_base).clone(), persistent=False)
+        # cos / sin of every position, fp32 [block_size, 2, head_dim / 2]; not a state_dict entry
+        self.register_buffer("rope", rope_table(cfg.block_size, cfg.rope_base, head_dim=cfg.n_embd // cfg.n_head).clone(),
+                             persistent=False)
         self.apply(self._init)
         for n, p in self.named_parameters():
             if n.endswith("wo.weight") or n.endswith("w2.weight"):

@@ -15,6 +15,12 @@ GPT-2-small and BERT-base.
 * :func:`pack_key_mask` — a [B, T] key-padding mask as the bits the kernels
   read (``key_mask=`` of both functions).
 
+Head dim 128 (``C // heads == 128``, the Llama-family shape) runs on a kernel
+family of its own (``csrc/kernels/attention_d128.hip``) behind the same two
+functions: softmax scale 1/sqrt(128), causal or not, packed gradient as at 64.
+It has no dropout and no key-padding mask: ``dropout_p > 0`` or a ``key_mask``
+at head dim 128 raises ``ValueError``.
+
 Key-padding mask. ``key_mask`` has the semantics of a boolean ``attn_mask`` of
 shape [B, 1, 1, T] in ``scaled_dot_product_attention``: True means the key
 takes part. A hidden key is excluded from the row max, the softmax normaliser
@@ -55,14 +61,35 @@ def _seed() -> int:
     return int(torch.randint(0, 2**62, (1,), dtype=torch.int64).item())
 
 
-def attn_shape_supported(T: int, C: int, heads: int) -> bool:
-    """Whether the kernels take sequence length T with C = heads * 64 channels."""
-    return bool(_C.attn_ok(T, C, heads))
+def _head_dim(head_dim: int) -> int:
+    if head_dim not in (64, 128):
+        raise ValueError(f"flash attention: head dim 64 or 128 required, got {head_dim}")
+    return head_dim
 
 
-def attn_supported(x: torch.Tensor, heads: int) -> bool:
+def attn_shape_supported(T: int, C: int, heads: int, head_dim: int = 64) -> bool:
+    """Whether the kernels take sequence length T with C = heads * head_dim channels."""
+    ok = _C.attn_ok if _head_dim(head_dim) == 64 else _C.attn128_ok
+    return bool(ok(T, C, heads))
+
+
+def attn_supported(x: torch.Tensor, heads: int, head_dim: int = 64) -> bool:
+    ok = _C.attn_ok if _head_dim(head_dim) == 64 else _C.attn128_ok
     return (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 3
-            and bool(_C.attn_ok(x.shape[1], x.shape[2], heads)))
+            and bool(ok(x.shape[1], x.shape[2], heads)))
+
+
+def _is_d128(C: int, heads: int, dropout_p: float, key_mask) -> bool:
+    """Whether a call with C channels takes the head-dim-128 kernels; their
+    limits are checked here, before any kernel call."""
+    if heads <= 0 or C != 128 * heads:
+        return False
+    if dropout_p > 0.0:
+        raise ValueError("flash attention at head dim 128 has no dropout (dropout_p must be 0; head dim 64 only)")
+    if key_mask is not None:
+        raise ValueError("flash attention at head dim 128 has no key-padding mask (key_mask must be None; "
+                         "head dim 64 only)")
+    return True
 
 
 def _km_args(km):
@@ -147,6 +174,49 @@ class _FlashAttnQKVFn(torch.autograd.Function):
         return dqkv, None, None, None, None, None, None, None
 
 
+def _bf16_grad(do):
+    do = do.contiguous()
+    return do if do.dtype == torch.bfloat16 else do.to(torch.bfloat16)
+
+
+class _FlashAttn128Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, heads, causal):
+        o, lse = _C.flash_attn128_fwd(q, k, v, heads, causal)
+        ctx.save_for_backward(q, k, v, o, lse)
+        ctx.cfg = (heads, causal)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        q, k, v, o, lse = ctx.saved_tensors
+        heads, causal = ctx.cfg
+        dq, dk, dv = (torch.empty_like(t, memory_format=torch.contiguous_format) for t in (q, k, v))
+        _C.flash_attn128_bwd(_bf16_grad(do), q, k, v, o, lse, heads, causal, dq, dk, dv)
+        return dq, dk, dv, None, None
+
+
+class _FlashAttn128QKVFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, qkv, heads, causal):
+        C = qkv.shape[2] // 3
+        o, lse = _C.flash_attn128_fwd(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], heads, causal)
+        ctx.save_for_backward(qkv, o, lse)
+        ctx.cfg = (heads, causal)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, o, lse = ctx.saved_tensors
+        heads, causal = ctx.cfg
+        C = qkv.shape[2] // 3
+        # the three gradients land in one packed buffer (no cat)
+        dqkv = torch.empty_like(qkv, memory_format=torch.contiguous_format)
+        _C.flash_attn128_bwd(_bf16_grad(do), qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], o, lse, heads, causal,
+                             dqkv[..., :C], dqkv[..., C:2 * C], dqkv[..., 2 * C:])
+        return dqkv, None, None
+
+
 def pack_key_mask(mask: torch.Tensor) -> torch.Tensor:
     """A key-padding mask [B, T] (bool, or an integer tensor of 0 / 1; T a
     multiple of 64; non-zero = the key takes part) as the kernels read it:
@@ -192,7 +262,9 @@ def _packed_key_mask(key_mask, B: int, T: int):
 def flash_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, causal: bool = False,
                dropout_p: float = 0.0, seed: int = None, key_mask: torch.Tensor = None,
                seed_offset: torch.Tensor = None) -> torch.Tensor:
-    """softmax(q kᵀ / 8 [+ causal mask] [+ key mask]) → dropout(p) → · v, per head of 64.
+    """softmax(q kᵀ / 8 [+ causal mask] [+ key mask]) → dropout(p) → · v, per head of 64;
+    with ``q.shape[2] == 128 * heads``: softmax(q kᵀ / sqrt(128) [+ causal mask]) · v per
+    head of 128 (no dropout, no key mask: ``ValueError``).
 
     ``key_mask``: a [B, T] bool key-padding mask (True = the key takes part;
     module docstring), packed on the spot by one small kernel, or the result
@@ -215,6 +287,8 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, ca
     fresh mask. An explicit ``seed=`` without ``seed_offset=`` keeps its plain
     meaning: the mask is that seed's, frozen under capture, the same on every
     replay."""
+    if _is_d128(q.shape[2], heads, float(dropout_p), key_mask):
+        return _FlashAttn128Fn.apply(q, k, v, heads, causal)
     host_seed, off = _seed_and_offset(q, float(dropout_p), seed, seed_offset)
     km = _packed_key_mask(key_mask, q.shape[0], q.shape[1])
     return _FlashAttnFn.apply(q, k, v, heads, causal, float(dropout_p), host_seed, _backward_will_run(q, k, v), km,
@@ -223,8 +297,10 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, ca
 
 def flash_attn_qkv(qkv: torch.Tensor, heads: int, causal: bool = False, dropout_p: float = 0.0,
                    seed: int = None, key_mask: torch.Tensor = None, seed_offset: torch.Tensor = None) -> torch.Tensor:
-    """:func:`flash_attn` on the three slices of a packed [B, T, 3*H*64]
-    projection (``key_mask``, ``seed`` and ``seed_offset`` as there)."""
+    """:func:`flash_attn` on the three slices of a packed [B, T, 3*H*64] (or
+    3*H*128) projection (``key_mask``, ``seed`` and ``seed_offset`` as there)."""
+    if qkv.shape[2] % 3 == 0 and _is_d128(qkv.shape[2] // 3, heads, float(dropout_p), key_mask):
+        return _FlashAttn128QKVFn.apply(qkv, heads, causal)
     host_seed, off = _seed_and_offset(qkv, float(dropout_p), seed, seed_offset)
     km = _packed_key_mask(key_mask, qkv.shape[0], qkv.shape[1])
     return _FlashAttnQKVFn.apply(qkv, heads, causal, float(dropout_p), host_seed, _backward_will_run(qkv), km, off)

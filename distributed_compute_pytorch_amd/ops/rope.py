@@ -1,15 +1,17 @@
 """Rotary position embedding on the packed qkv projection (csrc/kernels/rope.hip).
 
 ``apply_rope_qkv(qkv, heads, table)`` rotates the q and k thirds of a packed
-``[B, T, 3·heads·64]`` projection — the tensor ``flash_attn_qkv`` reads — and
-leaves v alone. Head dim 64, rotate-half pairing ``(i, i + 32)``::
+``[B, T, 3·heads·D]`` projection — the tensor ``flash_attn_qkv`` reads — and
+leaves v alone. Head dim D = 64 or 128, rotate-half pairing ``(i, i + h)``
+with h = D / 2::
 
-    y[i]      = x[i]·cos θ(t, i) − x[i + 32]·sin θ(t, i)
-    y[i + 32] = x[i + 32]·cos θ(t, i) + x[i]·sin θ(t, i)      θ(t, i) = t · base^(−i / 32)
+    y[i]     = x[i]·cos θ(t, i) − x[i + h]·sin θ(t, i)
+    y[i + h] = x[i + h]·cos θ(t, i) + x[i]·sin θ(t, i)      θ(t, i) = t · base^(−i / h)
 
-in fp32, rounded once. ``table = rope_table(T_max, base, device)`` holds
-cos / sin as fp32 ``[T_max, 2, 32]`` (``table[t, 0]`` = cos, ``table[t, 1]`` =
-sin), cached per (T_max, base, device); row ``t`` serves position ``t``.
+in fp32, rounded once. ``table = rope_table(T_max, base, device, head_dim)``
+holds cos / sin as fp32 ``[T_max, 2, h]`` (``table[t, 0]`` = cos, ``table[t, 1]``
+= sin), cached per (T_max, base, device, head_dim); row ``t`` serves position
+``t``. The ops take the head dim from the table's last dim.
 
 The backward is the rotation by −θ of the incoming packed gradient: it needs
 the table only, the forward saves nothing.
@@ -33,15 +35,18 @@ from .._ext import C as _C
 _TABLES: dict = {}
 
 
-def rope_table(T: int, base: float = 10000.0, device=None) -> torch.Tensor:
-    """fp32 [T, 2, 32]: cos (index 0) and sin (index 1) of t · base^(−i/32),
-    computed in fp64 and rounded once. Cached: build it outside graph capture
-    (the model does, at its first forward)."""
+def rope_table(T: int, base: float = 10000.0, device=None, head_dim: int = 64) -> torch.Tensor:
+    """fp32 [T, 2, h], h = head_dim / 2: cos (index 0) and sin (index 1) of
+    t · base^(−i/h), computed in fp64 and rounded once. Cached: build it
+    outside graph capture (the model does, at its first forward)."""
+    if head_dim not in (64, 128):
+        raise ValueError(f"rope_table: head dim 64 or 128 required, got {head_dim}")
+    h = head_dim // 2
     dev = torch.device(device) if device is not None else torch.device("cpu")
-    key = (int(T), float(base), dev)
+    key = (int(T), float(base), dev, h)
     t = _TABLES.get(key)
     if t is None:
-        inv = torch.tensor(float(base), dtype=torch.float64) ** (-torch.arange(32, dtype=torch.float64) / 32.0)
+        inv = torch.tensor(float(base), dtype=torch.float64) ** (-torch.arange(h, dtype=torch.float64) / float(h))
         ang = torch.arange(int(T), dtype=torch.float64)[:, None] * inv[None, :]
         t = _TABLES[key] = torch.stack([ang.cos(), ang.sin()], 1).to(torch.float32).contiguous().to(dev)
     return t
@@ -50,8 +55,10 @@ def rope_table(T: int, base: float = 10000.0, device=None) -> torch.Tensor:
 def rope_qkv_reference(qkv: torch.Tensor, heads: int, table: torch.Tensor, inverse: bool = False) -> torch.Tensor:
     """The definition, out of place, differentiable through autograd."""
     B, T, C3 = qkv.shape
-    if C3 != 3 * heads * 64:
-        raise ValueError(f"apply_rope_qkv: last dim must be 3*heads*64 = {3 * heads * 64}, got {C3}")
+    h = table.shape[2]
+    D = 2 * h
+    if C3 != 3 * heads * D:
+        raise ValueError(f"apply_rope_qkv: last dim must be 3*heads*{D} = {3 * heads * D}, got {C3}")
     if T > table.shape[0]:
         raise ValueError(f"apply_rope_qkv: sequence length {T} exceeds the table's {table.shape[0]} rows")
     ct = torch.float64 if qkv.dtype == torch.float64 else torch.float32
@@ -59,10 +66,10 @@ def rope_qkv_reference(qkv: torch.Tensor, heads: int, table: torch.Tensor, inver
     sin = table[:T, 1].to(device=qkv.device, dtype=ct)[None, :, None, :]
     if inverse:
         sin = -sin
-    qk = qkv[..., :2 * heads * 64].to(ct).reshape(B, T, 2 * heads, 64)
-    a, b = qk[..., :32], qk[..., 32:]
-    rot = torch.cat([a * cos - b * sin, b * cos + a * sin], -1).reshape(B, T, 2 * heads * 64)
-    return torch.cat([rot.to(qkv.dtype), qkv[..., 2 * heads * 64:]], -1)
+    qk = qkv[..., :2 * heads * D].to(ct).reshape(B, T, 2 * heads, D)
+    a, b = qk[..., :h], qk[..., h:]
+    rot = torch.cat([a * cos - b * sin, b * cos + a * sin], -1).reshape(B, T, 2 * heads * D)
+    return torch.cat([rot.to(qkv.dtype), qkv[..., 2 * heads * D:]], -1)
 
 
 class _RopeFn(torch.autograd.Function):
@@ -86,9 +93,9 @@ class _RopeFn(torch.autograd.Function):
 
 
 def apply_rope_qkv(qkv: torch.Tensor, heads: int, table: torch.Tensor, inplace: bool = False) -> torch.Tensor:
-    if (qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.dim() == 3 and qkv.shape[2] == 3 * heads * 64
-            and table.is_cuda and table.dtype == torch.float32 and tuple(table.shape[1:]) == (2, 32)
-            and table.is_contiguous()):
+    if (qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.dim() == 3 and table.dim() == 3
+            and table.is_cuda and table.dtype == torch.float32 and tuple(table.shape[1:]) in ((2, 32), (2, 64))
+            and qkv.shape[2] == 3 * heads * 2 * table.shape[2] and table.is_contiguous()):
         if qkv.shape[1] > table.shape[0]:
             raise ValueError(f"apply_rope_qkv: sequence length {qkv.shape[1]} exceeds the table's "
                              f"{table.shape[0]} rows")

@@ -5,8 +5,15 @@ cases run the BERT shape with a key-padding mask: ``bert-pad`` (per-sequence
 lengths drawn once from a seeded generator, uniform in [128, 512], right-padded)
 and ``bert-pad-full`` (an all-True mask: the price of carrying the mask);
 scaled_dot_product_attention gets the same boolean mask as [B, 1, 1, T].
+``llama-d128`` is the head-dim-128 kernel family at B8 T1024, 12 heads of 128,
+causal, no dropout (profiles/attn_d128_bench.jsonl: ``--cases llama-d128
+--iters 50 --repeat 5 --out profiles/attn_d128_bench.jsonl``).
 
-    python tools/attn_bench.py [--iters 10] [--graph 1]
+    python tools/attn_bench.py [--iters 10] [--graph 1] [--repeat 1] [--out FILE]
+
+--repeat N takes every timing N times, ours and SDPA alternating, and reports
+the median plus ``*_spread_us`` (max - min): the run-to-run spread a difference
+has to exceed.
 
 --graph 1 (default) times replays of a captured HIP graph of each call, so
 the numbers are GPU time (the eager loop's autograd / launch overhead per
@@ -55,21 +62,36 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--cases", nargs="*", default=None,
-                    help="subset of bert gpt2 bert-nodrop gpt2-nodrop bert-pad bert-pad-full")
+                    help="subset of bert gpt2 bert-nodrop gpt2-nodrop bert-pad bert-pad-full llama-d128")
     ap.add_argument("--graph", type=int, default=1)
+    ap.add_argument("--repeat", type=int, default=1)
+    ap.add_argument("--out", default=None, help="append the JSON lines to this file too")
     a = ap.parse_args()
     global GRAPH
     GRAPH = bool(a.graph)
     dev = torch.device("cuda", 0)
-    for name, B, T, H, causal, p, pad in [("bert", 32, 512, 12, False, 0.1, None),
-                                          ("gpt2", 8, 1024, 12, True, 0.1, None),
-                                          ("bert-nodrop", 32, 512, 12, False, 0.0, None),
-                                          ("gpt2-nodrop", 8, 1024, 12, True, 0.0, None),
-                                          ("bert-pad", 32, 512, 12, False, 0.1, "lengths"),
-                                          ("bert-pad-full", 32, 512, 12, False, 0.1, "full")]:
+
+    def pair(r, key, ours, sdpa):
+        """ours / SDPA timed a.repeat times, alternating; median (+ spread)"""
+        runs = {"ours": [], "sdpa": []}
+        for _ in range(a.repeat):
+            runs["ours"].append(timeit(ours, a.iters))
+            runs["sdpa"].append(timeit(sdpa, a.iters))
+        for who, ts in runs.items():
+            r[f"{who}_{key}_us"] = sorted(ts)[len(ts) // 2]
+            if a.repeat > 1:
+                r[f"{who}_{key}_spread_us"] = max(ts) - min(ts)
+
+    for name, B, T, H, causal, p, pad, D in [("bert", 32, 512, 12, False, 0.1, None, 64),
+                                             ("gpt2", 8, 1024, 12, True, 0.1, None, 64),
+                                             ("bert-nodrop", 32, 512, 12, False, 0.0, None, 64),
+                                             ("gpt2-nodrop", 8, 1024, 12, True, 0.0, None, 64),
+                                             ("bert-pad", 32, 512, 12, False, 0.1, "lengths", 64),
+                                             ("bert-pad-full", 32, 512, 12, False, 0.1, "full", 64),
+                                             ("llama-d128", 8, 1024, 12, True, 0.0, None, 128)]:
         if a.cases and name not in a.cases:
             continue
-        C = H * 64
+        C = H * D
         km = am = None  # the packed key mask (packed once, as a model does) / SDPA's boolean attn_mask
         if pad is not None:
             lens = torch.full((B,), T)
@@ -78,16 +100,15 @@ def main():
             mask = (torch.arange(T)[None, :] < lens[:, None]).to(dev)
             km, am = pack_key_mask(mask), mask[:, None, None, :]
         q, k, v, do = (torch.randn(B, T, C, device=dev, dtype=torch.bfloat16) for _ in range(4))
-        qs, ks, vs = (t.view(B, T, H, 64).transpose(1, 2) for t in (q, k, v))
-        fl = 4.0 * B * H * T * T * 64 * (0.5 if causal else 1.0)
-        r = {"case": name, "graph": GRAPH}
+        qs, ks, vs = (t.view(B, T, H, D).transpose(1, 2) for t in (q, k, v))
+        fl = 4.0 * B * H * T * T * D * (0.5 if causal else 1.0)
+        r = {"case": name, "graph": GRAPH, "iters": a.iters, "repeat": a.repeat}
         if pad is not None:
             r["mean_len"] = float(lens.float().mean())
         mkw = {} if km is None else {"key_mask": km}    # (no mask: the call of the unmasked cases, unchanged)
         skw = {} if am is None else {"attn_mask": am}
-        r["ours_fwd_us"] = timeit(lambda: flash_attn(q, k, v, H, causal, p, **mkw), a.iters)
-        r["sdpa_fwd_us"] = timeit(
-            lambda: F.scaled_dot_product_attention(qs, ks, vs, dropout_p=p, is_causal=causal, **skw), a.iters)
+        pair(r, "fwd", lambda: flash_attn(q, k, v, H, causal, p, **mkw),
+             lambda: F.scaled_dot_product_attention(qs, ks, vs, dropout_p=p, is_causal=causal, **skw))
         qa, ka, va = (t.clone().requires_grad_(True) for t in (q, k, v))
 
         # torch.autograd.grad: the gradients come back as new tensors, as in a
@@ -98,18 +119,21 @@ def main():
             torch.autograd.grad(flash_attn(qa, ka, va, H, causal, p, **mkw), (qa, ka, va), do)
 
         qsa, ksa, vsa = (t.clone().requires_grad_(True) for t in (qs, ks, vs))
-        dos = do.view(B, T, H, 64).transpose(1, 2)
+        dos = do.view(B, T, H, D).transpose(1, 2)
 
         def sdpa_fb():
             torch.autograd.grad(
                 F.scaled_dot_product_attention(qsa, ksa, vsa, dropout_p=p, is_causal=causal, **skw),
                 (qsa, ksa, vsa), dos)
 
-        r["ours_fwdbwd_us"] = timeit(ours_fb, a.iters)
-        r["sdpa_fwdbwd_us"] = timeit(sdpa_fb, a.iters)
+        pair(r, "fwdbwd", ours_fb, sdpa_fb)
         r["ours_fwd_TFps"] = fl / (r["ours_fwd_us"] * 1e-6) / 1e12
         r["ours_fwdbwd_TFps"] = 3.5 * fl / (r["ours_fwdbwd_us"] * 1e-6) / 1e12
-        print(json.dumps({kk: (round(vv, 1) if isinstance(vv, float) else vv) for kk, vv in r.items()}), flush=True)
+        line = json.dumps({kk: (round(vv, 1) if isinstance(vv, float) else vv) for kk, vv in r.items()})
+        print(line, flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(line + "\n")
 
 
 if __name__ == "__main__":

@@ -25,6 +25,9 @@ void bind(pybind11::module& m);
 namespace attn128 {
 void bind(pybind11::module& m);
 }
+namespace fp8 {
+void bind(pybind11::module& m);
+}
 }  // namespace dcp
 #include "trace/trace.h"
 #include "store/tcp_store.h"
@@ -271,4 +274,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   llama::bind(m);
   augment::bind(m);
   attn128::bind(m);
+  fp8::bind(m);
 }

@@ -100,6 +100,9 @@ _FILE_FLAGS = {
     # per row of 8 logits per lane otherwise (the bf16 unpacks and DPP moves
     # are not known canonical); the file tests ±inf, never NaN
     "kernels/gemm_pp.hip": ["-fno-honor-nans"],
+    # the fp8 quantiser and GEMM: new code, so no packed-fp32 VALU forms (the
+    # epilogue's scale multiplies and bias adds would otherwise pair up)
+    "kernels/gemm_fp8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

@@ -30,6 +30,13 @@ attention dropout, so a fused model with ``dropout > 0`` in training takes
 ``scaled_dot_product_attention`` for the attention core at that width (the
 rest of the block stays fused).
 
+``LlamaConfig(fp8=True)`` (opt-in, default off; fused models only): the two
+un-packed projections of every block, ``attention.wo`` and ``feed_forward.w2``,
+run their forward and data-gradient GEMMs in row-scaled fp8 (``ops/fp8.py``:
+e4m3 activations and weights, e5m2 output gradients). The packed ``wq|wk|wv``
+and ``w1|w3`` GEMMs, every weight gradient and the head stay bf16. Parameters
+and ``state_dict`` are unchanged; off the bf16 GPU path nothing differs.
+
 Out of scope: grouped-query attention (the attention kernels take equal q and
 k head counts), head dims other than 64 and 128, KV-cache decoding.
 """
@@ -45,6 +52,7 @@ from torch.nn import functional as F
 from ..ops.attention import attn_supported, flash_attn_qkv
 from ..ops.dropout import dropout_add
 from ..ops.embedding import FusedEmbedding
+from ..ops.fp8 import Fp8Linear
 from ..ops.linear import FusedLinear, LinearWeightPrep, _LinearFn, _PackedLinearFn, packed_linear, prepped_linear
 from ..ops.lm_head import lm_head_cross_entropy, padded_vocab
 from ..ops.rmsnorm import FusedRMSNorm
@@ -64,6 +72,7 @@ class LlamaConfig:
     dropout: float = 0.0
     tie_embeddings: bool = False
     norm_eps: float = 1e-6
+    fp8: bool = False  # wo / w2 forward and data gradient in fp8 (fused models; module docstring)
 
 
 _ZERO_BIAS: dict = {}
@@ -101,6 +110,19 @@ class BiasFreeLinear(FusedLinear):
         return F.linear(x, self.weight)
 
 
+class BiasFreeFp8Linear(Fp8Linear):
+    """Bias-free :class:`Fp8Linear`; where the fp8 path does not apply it is
+    :class:`BiasFreeLinear`."""
+
+    def __init__(self, in_features: int, out_features: int):
+        super().__init__(in_features, out_features, bias=False)
+
+    def forward(self, x):
+        if self._fp8_fast(x):
+            return self._forward_fp8(x)
+        return BiasFreeLinear.forward(self, x)
+
+
 def _packed_bias_free(x: torch.Tensor, layers) -> torch.Tensor:
     """``packed_linear`` for bias-free layers: the same one-GEMM node, handed
     the zero bias; off the bf16 GPU path it is ``packed_linear`` itself."""
@@ -133,7 +155,8 @@ class Attention(nn.Module):
         super().__init__()
         lin = BiasFreeLinear if fused else (lambda i, o: nn.Linear(i, o, bias=False))
         C = cfg.n_embd
-        self.wq, self.wk, self.wv, self.wo = lin(C, C), lin(C, C), lin(C, C), lin(C, C)
+        self.wq, self.wk, self.wv = lin(C, C), lin(C, C), lin(C, C)
+        self.wo = (BiasFreeFp8Linear if fused and cfg.fp8 else lin)(C, C)
         self.n_head, self.dropout, self.fused = cfg.n_head, cfg.dropout, fused
         self.head_dim = C // cfg.n_head
 
@@ -166,7 +189,7 @@ class FeedForward(nn.Module):
         lin = BiasFreeLinear if fused else (lambda i, o: nn.Linear(i, o, bias=False))
         self.w1 = lin(cfg.n_embd, cfg.ffn_hidden)  # gate
         self.w3 = lin(cfg.n_embd, cfg.ffn_hidden)  # up
-        self.w2 = lin(cfg.ffn_hidden, cfg.n_embd)  # down
+        self.w2 = (BiasFreeFp8Linear if fused and cfg.fp8 else lin)(cfg.ffn_hidden, cfg.n_embd)  # down
         self.fused = fused
 
     def forward(self, x):

@@ -4,6 +4,11 @@ data-gradient GEMM (_C.conv1x1_dgrad) vs hipBLASLt through torch, under each
 requested gemm_tune setting. One JSON line per (shape, op).
 
     python tools/linear_bench.py [--iters 20] [--tune lin_big=0 lin_big=1 lin_big=2 nt_big=2]
+
+``--fp8``: the fp8 Linear GEMMs (ops/fp8.py) against the bf16 candidates of
+ops/linear.py at M = 8192, forward and data gradient: ``gemm_fp8`` alone and
+quantiser + GEMM, every candidate timed in turn within each of ``--reps``
+rounds (median, min, max over the rounds, in µs).
 """
 import argparse
 import json
@@ -63,6 +68,50 @@ def wgrad(model, M, K, N, x, gy, a):
     print(json.dumps(rec), flush=True)
 
 
+FP8_SHAPES = [(768, 768), (2048, 768), (4096, 4096), (11008, 4096)]  # (K, N) at M = 8192
+
+
+def fp8_bench(a, dev):
+    import statistics
+
+    from distributed_compute_pytorch_amd.ops import linear as lin
+    from distributed_compute_pytorch_amd.ops.fp8 import quantize_weight
+
+    bf, M = torch.bfloat16, 8192
+    for K, N in FP8_SHAPES:
+        x = torch.randn(M, K, device=dev).to(bf)
+        gy = torch.randn(M, N, device=dev).to(bf)
+        w = (0.02 * torch.randn(N, K, device=dev)).to(bf)
+        wt = w.t().contiguous()
+        b32 = torch.zeros(N, device=dev)
+        w8, sw, wt8, swt = quantize_weight(w, wt)
+        xq, sx = _C.fp8_quant_rows(x, 0)
+        gq, sg = _C.fp8_quant_rows(gy, 1)
+        ops = {
+            "fwd": ({"fp8_gemm": lambda: _C.gemm_fp8(xq, sx, w8, sw, b32, 0),
+                     "fp8_quant_gemm": lambda: _C.gemm_fp8(*_C.fp8_quant_rows(x, 0), w8, sw, b32, 0)},
+                    lin._fwd_cands(x, w, b32.to(bf), b32, 0) if lin._gemm_ok(x, w, b32)
+                    else {"hipblaslt": lambda: F.linear(x, w)}),
+            "dgrad": ({"fp8_gemm": lambda: _C.gemm_fp8(gq, sg, wt8, swt, None, 1),
+                       "fp8_quant_gemm": lambda: _C.gemm_fp8(*_C.fp8_quant_rows(gy, 1), wt8, swt, None, 1)},
+                      lin._dgrad_cands(gy, w, wt) if N <= 4096 else {"hipblaslt": lambda: gy @ w}),
+        }
+        for op, (fp8, bf16) in ops.items():
+            cands = {**fp8, **{"bf16_" + k: v for k, v in bf16.items()}}
+            us = {k: [] for k in cands}
+            for _ in range(a.reps):
+                for k, fn in cands.items():
+                    us[k].append(timeit(fn, a.iters))
+            rec = {"M": M, "K": K, "N": N, "op": op, "iters": a.iters, "reps": a.reps}
+            for k, v in us.items():
+                rec[k] = {"median": round(statistics.median(v), 1), "min": round(min(v), 1), "max": round(max(v), 1)}
+            best = min((k for k in cands if k.startswith("bf16_")), key=lambda k: rec[k]["median"])
+            rec["best_bf16"] = best
+            rec["fp8_gemm_vs_bf16"] = round(rec[best]["median"] / rec["fp8_gemm"]["median"], 3)
+            rec["fp8_quant_gemm_vs_bf16"] = round(rec[best]["median"] / rec["fp8_quant_gemm"]["median"], 3)
+            print(json.dumps(rec), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
@@ -70,8 +119,12 @@ def main():
     ap.add_argument("--wg-variants", nargs="*", default=WG_VARIANTS, help="gemm_tune settings of the wgrad A/B")
     ap.add_argument("--wgrad3", action="store_true", help="ResNet-50 3x3 weight gradients under each --tune entry")
     ap.add_argument("--tune", nargs="*", default=["lin_big=0", "lin_big=1", "lin_big=2"])
+    ap.add_argument("--fp8", action="store_true", help="fp8 Linear GEMMs vs the bf16 candidates (M = 8192)")
+    ap.add_argument("--reps", type=int, default=5, help="--fp8: rounds over the alternating candidates")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
+    if a.fp8:
+        return fp8_bench(a, dev)
     bf = torch.bfloat16
     if a.wgrad3:
         for hw, c in [(28, 128), (14, 256), (7, 512)]:

@@ -103,6 +103,8 @@ _FILE_FLAGS = {
     # the fp8 quantiser and GEMM: new code, so no packed-fp32 VALU forms (the
     # epilogue's scale multiplies and bias adds would otherwise pair up)
     "kernels/gemm_fp8.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    # the fp8 weight gradient: the same (the float4 epilogues and the slab reduction)
+    "kernels/gemm_fp8_wgrad.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

@@ -34,8 +34,11 @@ rest of the block stays fused).
 un-packed projections of every block, ``attention.wo`` and ``feed_forward.w2``,
 run their forward and data-gradient GEMMs in row-scaled fp8 (``ops/fp8.py``:
 e4m3 activations and weights, e5m2 output gradients). The packed ``wq|wk|wv``
-and ``w1|w3`` GEMMs, every weight gradient and the head stay bf16. Parameters
-and ``state_dict`` are unchanged; off the bf16 GPU path nothing differs.
+and ``w1|w3`` GEMMs, every weight gradient and the head stay bf16.
+``fp8_wgrad=True`` (opt-in too; requires ``fp8=True``) moves the weight
+gradients of ``wo`` and ``w2`` to the column-scaled fp8 GEMM as well
+(``Fp8Linear.wgrad = "fp8"``). Parameters and ``state_dict`` are unchanged;
+off the bf16 GPU path nothing differs.
 
 Out of scope: grouped-query attention (the attention kernels take equal q and
 k head counts), head dims other than 64 and 128, KV-cache decoding.
@@ -73,6 +76,11 @@ class LlamaConfig:
     tie_embeddings: bool = False
     norm_eps: float = 1e-6
     fp8: bool = False  # wo / w2 forward and data gradient in fp8 (fused models; module docstring)
+    fp8_wgrad: bool = False  # their weight gradients in fp8 too (requires fp8)
+
+    def __post_init__(self):
+        if self.fp8_wgrad and not self.fp8:
+            raise ValueError("LlamaConfig: fp8_wgrad=True requires fp8=True")
 
 
 _ZERO_BIAS: dict = {}
@@ -157,6 +165,8 @@ class Attention(nn.Module):
         C = cfg.n_embd
         self.wq, self.wk, self.wv = lin(C, C), lin(C, C), lin(C, C)
         self.wo = (BiasFreeFp8Linear if fused and cfg.fp8 else lin)(C, C)
+        if fused and cfg.fp8_wgrad:
+            self.wo.wgrad = "fp8"
         self.n_head, self.dropout, self.fused = cfg.n_head, cfg.dropout, fused
         self.head_dim = C // cfg.n_head
 
@@ -190,6 +200,8 @@ class FeedForward(nn.Module):
         self.w1 = lin(cfg.n_embd, cfg.ffn_hidden)  # gate
         self.w3 = lin(cfg.n_embd, cfg.ffn_hidden)  # up
         self.w2 = (BiasFreeFp8Linear if fused and cfg.fp8 else lin)(cfg.ffn_hidden, cfg.n_embd)  # down
+        if fused and cfg.fp8_wgrad:
+            self.w2.wgrad = "fp8"
         self.fused = fused
 
     def forward(self, x):

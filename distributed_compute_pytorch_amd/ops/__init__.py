@@ -12,11 +12,13 @@ from .rope import apply_rope_qkv, rope_table
 from .swiglu import swiglu
 from .augment import (center_crop_params, crop_resize_normalize, crop_resize_normalize_reference,
                       random_resized_crop_params)
-from .fp8 import Fp8Linear, fp8_linear, quantize_rows, quantize_rows_reference
+from .fp8 import (Fp8Linear, fp8_linear, fp8_weight_grad, quantize_cols_t, quantize_cols_t_reference, quantize_rows,
+                  quantize_rows_reference)
 
 __all__ = ["BatchNormAct1d", "BatchNormAct2d", "bn_act", "FusedLayerNorm", "fused_layer_norm", "fused_cross_entropy",
            "FusedDropout", "FusedDropout2d", "dropout_add", "fused_dropout", "fused_feature_dropout",
            "FusedMaxPool2d", "fused_max_pool2d", "relu_max_pool2d_dropout", "fused_log_softmax", "EvalMetrics",
            "convnet_features", "fc32", "FusedRMSNorm", "fused_rms_norm", "apply_rope_qkv", "rope_table", "swiglu",
            "crop_resize_normalize", "crop_resize_normalize_reference", "random_resized_crop_params",
-           "center_crop_params", "Fp8Linear", "fp8_linear", "quantize_rows", "quantize_rows_reference"]
+           "center_crop_params", "Fp8Linear", "fp8_linear", "quantize_rows", "quantize_rows_reference",
+           "fp8_weight_grad", "quantize_cols_t", "quantize_cols_t_reference"]

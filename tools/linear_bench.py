@@ -8,7 +8,11 @@ requested gemm_tune setting. One JSON line per (shape, op).
 ``--fp8``: the fp8 Linear GEMMs (ops/fp8.py) against the bf16 candidates of
 ops/linear.py at M = 8192, forward and data gradient: ``gemm_fp8`` alone and
 quantiser + GEMM, every candidate timed in turn within each of ``--reps``
-rounds (median, min, max over the rounds, in µs).
+rounds (median, min, max over the rounds, in µs). Its ``wgrad`` op: the fp8
+weight-gradient GEMM alone (at the host's split count, and at each of
+``--wgrad-splits``), both column quantisers + GEMM, and the bf16
+``_C.conv1x1_wgrad`` it would replace (``--ops wgrad`` for that op alone; kept
+in ``profiles/fp8_wgrad_bench.jsonl``).
 """
 import argparse
 import json
@@ -87,6 +91,12 @@ def fp8_bench(a, dev):
         w8, sw, wt8, swt = quantize_weight(w, wt)
         xq, sx = _C.fp8_quant_rows(x, 0)
         gq, sg = _C.fp8_quant_rows(gy, 1)
+        gqt, sgt = _C.fp8_quant_cols_t(gy, 1)
+        xqt, sxt = _C.fp8_quant_cols_t(x, 0)
+        wg = {"fp8_gemm": lambda: _C.gemm_fp8_wgrad(gqt, sgt, xqt, sxt, 1),
+              "fp8_quant_gemm": lambda: _C.gemm_fp8_wgrad(*_C.fp8_quant_cols_t(gy, 1), *_C.fp8_quant_cols_t(x, 0), 1)}
+        for S in a.wgrad_splits:
+            wg[f"fp8_gemm_S{S}"] = lambda S=S: _C.gemm_fp8_wgrad(gqt, sgt, xqt, sxt, 1, splits=S)
         ops = {
             "fwd": ({"fp8_gemm": lambda: _C.gemm_fp8(xq, sx, w8, sw, b32, 0),
                      "fp8_quant_gemm": lambda: _C.gemm_fp8(*_C.fp8_quant_rows(x, 0), w8, sw, b32, 0)},
@@ -95,14 +105,19 @@ def fp8_bench(a, dev):
             "dgrad": ({"fp8_gemm": lambda: _C.gemm_fp8(gq, sg, wt8, swt, None, 1),
                        "fp8_quant_gemm": lambda: _C.gemm_fp8(*_C.fp8_quant_rows(gy, 1), wt8, swt, None, 1)},
                       lin._dgrad_cands(gy, w, wt) if N <= 4096 else {"hipblaslt": lambda: gy @ w}),
+            "wgrad": (wg, {"wgrad": lambda: _C.conv1x1_wgrad(gy, x, slots=lin._wgrad_slots(M))}),
         }
         for op, (fp8, bf16) in ops.items():
+            if op not in a.ops:
+                continue
             cands = {**fp8, **{"bf16_" + k: v for k, v in bf16.items()}}
             us = {k: [] for k in cands}
             for _ in range(a.reps):
                 for k, fn in cands.items():
                     us[k].append(timeit(fn, a.iters))
             rec = {"M": M, "K": K, "N": N, "op": op, "iters": a.iters, "reps": a.reps}
+            if op == "wgrad":
+                rec["auto_splits"] = _C.gemm_fp8_wgrad_splits(N, K, M)
             for k, v in us.items():
                 rec[k] = {"median": round(statistics.median(v), 1), "min": round(min(v), 1), "max": round(max(v), 1)}
             best = min((k for k in cands if k.startswith("bf16_")), key=lambda k: rec[k]["median"])
@@ -121,6 +136,8 @@ def main():
     ap.add_argument("--tune", nargs="*", default=["lin_big=0", "lin_big=1", "lin_big=2"])
     ap.add_argument("--fp8", action="store_true", help="fp8 Linear GEMMs vs the bf16 candidates (M = 8192)")
     ap.add_argument("--reps", type=int, default=5, help="--fp8: rounds over the alternating candidates")
+    ap.add_argument("--ops", nargs="*", default=["fwd", "dgrad", "wgrad"], help="--fp8: the ops to time")
+    ap.add_argument("--wgrad-splits", nargs="*", type=int, default=[], help="--fp8 wgrad: explicit split counts to add")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     if a.fp8:

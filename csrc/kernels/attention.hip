@@ -2,22 +2,16 @@
 // v_mfma_f32_32x32x16_bf16, bf16 I/O, fp32 online softmax, optional causal
 // mask and dropout on P (keep bits hashed in the forward, stored for the backward).
 //
-// Layout choices (CDNA4, wave64):
-//  * "swapped" products: the forward computes Sᵀ = K·Qᵀ so each lane owns one
-//    query (its 32 key scores sit in the lane's accumulator registers, the
-//    other 32 in lane^32): row max / row sum are in-lane plus ONE shfl_xor(32).
-//  * the Sᵀ accumulator is directly the B operand of Oᵀ += Vᵀ·P (accumulator-
-//    as-operand, CDNA4 guide §3): no LDS round trip for P; the matching Vᵀ
-//    operand is read with ds_read_b64_tr_b16 (hardware transpose) from the
-//    row-major V tile.
-//  * every LDS tile is [64 rows][64 bf16] (128-B rows) with one XOR swizzle
-//    that is conflict-free for both the 16-B row reads (16 consecutive rows)
-//    and the transposed reads (4 rows × 32 B per 16-lane group).
-//  * K/V (or Q/dO) tiles arrive by global_load_lds (async DMA) into a 2-deep
-//    ring, one barrier per tile.
-//  * backward = two kernels (FA2 split, no float atomics): dK/dV with the key
-//    on the lane (S and dP accumulators feed dVᵀ += dOᵀ·P and dKᵀ += Qᵀ·dS
-//    directly), and dQ with the query on the lane (dQᵀ += Kᵀ·dSᵀ).
+// The design shared with head dim 128 is in attn_mma.h, with its reasons: the
+// "swapped" products with one query (forward, dQ) or one key (dK/dV) per lane,
+// the accumulator as the B operand of the second product, the swizzled tile
+// image, the 2-deep DMA ring, the FA2 split of the backward and the causal
+// serpentine work order.
+//
+// What is particular to 64:
+//  * every LDS tile is [64 rows][64 bf16] (128-B rows, swz<64>): 8 KiB = 8
+//    wave-instructions of DMA, 2 per wave; both 32-query sub-tiles of dK/dV
+//    are in flight at once (two accumulators per product, not four).
 //  * dropout: the forward hashes, and stores the keep decisions as bits (T²/8
 //    bytes per head, in a word order both backward kernels read directly);
 //    the backward hashes nothing.
@@ -46,17 +40,13 @@
 
 #include <cmath>
 
-#include "attn_kernels.h"
-#include "bf16_vec.h"
+#include "attn_mma.h"
 
 namespace dcp {
 namespace kern {
 namespace {
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+using namespace attndev;  // fragments, tile image, DMA plan, work order (attn_mma.h)
 
 constexpr int kT = 256;
 constexpr int kD = 64;
@@ -64,111 +54,9 @@ constexpr int kKB = 64;               // rows per LDS tile
 constexpr int kTile = kKB * kD * 2;   // 8 KiB
 constexpr float kLog2e = 1.4426950408889634f;
 
-__device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) z[r] = 0.f;
-  return z;
-}
 // an all-ones bf16 operand fragment (1.0 = 0x3F80)
 __device__ __forceinline__ bf16x8 ones_frag() {
   return __builtin_bit_cast(bf16x8, make_uint4(0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u));
-}
-// registers 8s … 8s+7 of an accumulator → bf16 operand fragment of k-step s
-__device__ __forceinline__ bf16x8 acc_frag(const f32x16& a, int s) {
-  const uint4 u = make_uint4(pack2(a[8 * s + 0], a[8 * s + 1]), pack2(a[8 * s + 2], a[8 * s + 3]),
-                             pack2(a[8 * s + 4], a[8 * s + 5]), pack2(a[8 * s + 6], a[8 * s + 7]));
-  return __builtin_bit_cast(bf16x8, u);
-}
-
-// ---- LDS tile image [64][64] bf16: 16-B chunk c of row r at r*128 + 16*(c ^ swz(r)).
-// Row reads (16 consecutive rows, one chunk) and transposed reads (rows R..R+3
-// and R+4.., chunks 0-3 or 4-7 per 32-lane half) both hit distinct bank slots.
-__device__ __forceinline__ int swz(int r) { return (((r >> 1) & 1) << 2) | ((r >> 2) & 3); }
-__device__ __forceinline__ int img(int r, int c) { return r * 128 + 16 * (c ^ swz(r)); }
-
-__device__ __forceinline__ bf16x8 row_rd(const char* base, int r, int c) {
-  return *reinterpret_cast<const bf16x8*>(base + img(r, c));
-}
-
-// Operand A[x][row] = tile[row][x] for "A · X" with X an accumulator tile used
-// as the B operand: element j of lane l ↔ tile row rbase + 8(j>>2) + 4(l>>5) +
-// (j&3), column dcol0 + (l&31) — two ds_read_b64_tr_b16.
-__device__ __forceinline__ bf16x8 tr_op(const char* base, int rbase, int dcol0, int lane) {
-  const int g = lane >> 4, hh = lane >> 5, q = (lane >> 2) & 3, p = lane & 3;
-  const int c0 = dcol0 + 16 * (g & 1);
-  const int r0 = rbase + 4 * hh + q;
-  const int ch = (c0 >> 3) + (p >> 1);
-  const char* a0 = base + img(r0, ch) + 8 * (p & 1);
-  const char* a1 = base + img(r0 + 8, ch) + 8 * (p & 1);
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a1));
-  const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, v);
-}
-
-// LDS DMA (16 / 4 B per lane) into the wave-uniform LDS address lds_dst (+
-// lane x size). Inline asm on purpose: a compiler-visible global_load_lds is a
-// pending LDS write to hipcc, which then put s_waitcnt vmcnt(0) before the
-// first LDS read after it — in every loop iteration, so each tile waited for
-// the NEXT tile's DMA to land in the middle of its own compute (PMC r5: 0.3 of
-// wave cycles waiting, MFMA busy 0.14-0.22). Hidden, the ring is ordered by
-// the explicit wait_vm0 + barrier at the top of each iteration only. M0 is
-// compiler-reserved: set and restored in-statement. The source is a
-// wave-uniform 64-bit base in SGPRs plus a 32-bit per-lane byte offset
-// (saddr form): the per-lane part of a tile's source is
-// loop-invariant, so each DMA costs no VALU address arithmetic (the 64-bit
-// per-lane pointer form recomputed row × stride with two v_mad_u64_u32 and
-// moves per DMA, ~20 VALU per key block)
-__device__ __forceinline__ uint32_t lds_u32(const char* p) {
-  return __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(reinterpret_cast<uintptr_t>(p)));
-}
-__device__ __forceinline__ void glds16s(const void* sbase, uint32_t voff, char* lds_dst) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(sbase), "s"(lds_u32(lds_dst))
-               : "memory");
-}
-__device__ __forceinline__ void glds4s(const void* sbase, uint32_t voff, char* lds_dst) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(sbase), "s"(lds_u32(lds_dst))
-               : "memory");
-}
-__device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
-// DMA rows [r0, r0+64) of a strided [T][64] head slice into a tile image;
-// 4 waves × 2 wave-instructions of 1 KiB (8 rows each). TileOff: this lane's
-// byte offsets within the 64-row slab (row u / 8, swizzled chunk), computed
-// once per tensor; the slab base src + r0 · st is wave-uniform.
-struct TileOff {
-  uint32_t o[2];
-};
-__device__ __forceinline__ TileOff tile_off(int64_t st, int wave, int lane) {
-  TileOff t;
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int u = (wave * 2 + j) * 64 + lane;  // 16-B unit of the image
-    const int r = u >> 3, lc = (u & 7) ^ swz(u >> 3);
-    t.o[j] = static_cast<uint32_t>((r * st + lc * 8) * 2);
-  }
-  return t;
-}
-__device__ __forceinline__ void stage_tile(const uint16_t* src, int64_t st, int r0, const TileOff& to, char* dst,
-                                           int wave) {
-  const uint16_t* base = src + static_cast<int64_t>(r0) * st;
-#pragma unroll
-  for (int j = 0; j < 2; ++j) glds16s(base, to.o[j], dst + (wave * 2 + j) * 1024);
 }
 
 // ---- dropout: 8 random bits per element (q, key) — byte thresholds, the
@@ -243,20 +131,6 @@ __device__ __forceinline__ int64_t mask_word(int bh, int nblk, int kblk, int hh,
   return ((static_cast<int64_t>(bh) * nblk + kblk) * 2 + hh) * T + q;
 }
 
-// combine x with the lane 32 apart (lane ^ 32): gfx950's v_permlane32_swap
-// (a VALU lane exchange) instead of __shfl_xor's ds_bpermute round trip
-// through LDS on the softmax's critical path. With both operands x, the two
-// results hold x and its partner in some order in every lane; max / + are
-// symmetric, so every lane gets the same combined value
-__device__ __forceinline__ float max_xor32(float x) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float sum_xor32(float x) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
 // a wave-uniform 64-bit value into scalar registers (a key-mask word loaded
 // inside the tile loop comes back in vector registers: after the DMA asm's
 // memory clobber hipcc no longer selects a scalar load for it)
@@ -264,42 +138,6 @@ __device__ __forceinline__ uint64_t uniform64(uint64_t x) {
   const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x));
   const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x >> 32));
   return (static_cast<uint64_t>(hi) << 32) | lo;
-}
-
-// (batch-head, tile) of this workgroup. Causal: tiles carry unequal work
-// (query tile t of the forward / dQ sees t + 1 key tiles; key tile t of dK/dV
-// is seen by nt - t query tiles). Workgroups are dispatched breadth-first, so
-// CU c receives launch positions c, c + 256, c + 512, …; with the work items
-// sorted heaviest first, odd rounds of 256 take them in reverse (serpentine)
-// so every CU's set sums to about the mean instead of heavy + heavy + medium.
-// heavy_last: the heaviest tile is the last one (forward, dQ) or tile 0 (dK/dV).
-__device__ __forceinline__ void attn_item(bool causal, bool heavy_last, int& bh, int& tile) {
-  const int nbh = static_cast<int>(gridDim.x), nt = static_cast<int>(gridDim.y);
-  if (!causal) {
-    bh = static_cast<int>(blockIdx.x);
-    tile = static_cast<int>(blockIdx.y);
-    return;
-  }
-  const int L = static_cast<int>(blockIdx.y) * nbh + static_cast<int>(blockIdx.x);
-  const int G = nbh * nt;
-  constexpr int C = 256;
-  const int r = L / C, pos = L % C;
-  int I = L;
-  if (r & 1) {
-    const int end = min(G, (r + 1) * C);  // a partial last round reverses within itself
-    I = end - 1 - pos;
-  }
-  bh = I % nbh;
-  const int rank = I / nbh;  // 0 = heaviest
-  tile = heavy_last ? nt - 1 - rank : rank;
-}
-
-struct Ptrs {
-  const uint16_t* p;
-  int64_t st;
-};
-__device__ __forceinline__ Ptrs head(const AttnTensor& t, int b, int hd) {
-  return Ptrs{static_cast<const uint16_t*>(t.ptr) + b * t.sb + hd * kD, t.st};
 }
 
 // ------------------------------------------------------------ forward ----
@@ -317,13 +155,14 @@ __global__ void __launch_bounds__(kT) attn_fwd_kernel(AttnParams P, AttnTensor q
   const int T = P.T;
   const int qi = tile * 128 + wave * 32 + (lane & 31);  // this lane's query
   const bool qok = qi < T;
-  const Ptrs Q = head(q, b, hd), K = head(k, b, hd), V = head(v, b, hd);
+  const Ptrs Q = head<kD>(q, b, hd), K = head<kD>(k, b, hd), V = head<kD>(v, b, hd);
 
   bf16x8 qf[4];
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) {
-    // load (row clamped), then select: `ok ? *p : zero` becomes a pointer
-    // select to a scratch copy of the zero (flat loads + scratch stores)
+    // load (row clamped), then select (load_row has the reason). Open-coded
+    // here and in the two backward kernels: through load_row hipcc allocates
+    // this file's kernels differently (other SGPR counts, NOTES §47)
     const uint4 z = make_uint4(0, 0, 0, 0);
     const uint4 u = *reinterpret_cast<const uint4*>(Q.p + static_cast<int64_t>(qok ? qi : 0) * Q.st + 16 * ks + 8 * hh);
     qf[ks] = __builtin_bit_cast(bf16x8, qok ? u : z);
@@ -355,7 +194,7 @@ __global__ void __launch_bounds__(kT) attn_fwd_kernel(AttnParams P, AttnTensor q
     kwnext = KM[1];
   }
 
-  const TileOff ko = tile_off(K.st, wave, lane), vo = tile_off(V.st, wave, lane);
+  const TileOff<kD> ko = tile_off<kD>(K.st, wave, lane), vo = tile_off<kD>(V.st, wave, lane);
   auto issue = [&](int it) {
     if (it >= nkb) return;
     char* base = lds + (it & 1) * 2 * kTile;
@@ -385,7 +224,7 @@ __global__ void __launch_bounds__(kT) attn_fwd_kernel(AttnParams P, AttnTensor q
     for (int kh = 0; kh < 2; ++kh) {
       s[kh] = zero16();
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) s[kh] = mfma(row_rd(sK, 32 * kh + (lane & 31), 2 * ks + hh), qf[ks], s[kh]);
+      for (int ks = 0; ks < 4; ++ks) s[kh] = mfma(row_rd<kD>(sK, 32 * kh + (lane & 31), 2 * ks + hh), qf[ks], s[kh]);
     }
     // s[kh][r]: key kb + 32kh + (r&3) + 8(r>>2) + 4hh, query qi. Raw scores:
     // the max is taken before scaling (c > 0) and the scale is folded into
@@ -477,7 +316,7 @@ __global__ void __launch_bounds__(kT) attn_fwd_kernel(AttnParams P, AttnTensor q
         }
         const bf16x8 pf = __builtin_bit_cast(bf16x8, u);
 #pragma unroll
-        for (int dh = 0; dh < 2; ++dh) oacc[dh] = mfma(tr_op(sV, 32 * kh + 16 * sg, 32 * dh, lane), pf, oacc[dh]);
+        for (int dh = 0; dh < 2; ++dh) oacc[dh] = mfma(tr_op<kD>(sV, 32 * kh + 16 * sg, 32 * dh, lane), pf, oacc[dh]);
       }
     if (DROP && qok && P.mask != nullptr) P.mask[mask_word(bh, T / kKB, it, hh, T, qi)] = word;
     if (DROP) l = l * alpha + lsum[0];
@@ -520,7 +359,8 @@ __global__ void __launch_bounds__(kT) attn_bwd_dq_kernel(AttnCoreParams P, AttnT
   const int T = P.T;
   const int qi = tile * 128 + wave * 32 + (lane & 31);
   const bool qok = qi < T;
-  const Ptrs Q = head(q, b, hd), K = head(k, b, hd), V = head(v, b, hd), G = head(dout, b, hd), O = head(o, b, hd);
+  const Ptrs Q = head<kD>(q, b, hd), K = head<kD>(k, b, hd), V = head<kD>(v, b, hd), G = head<kD>(dout, b, hd),
+             O = head<kD>(o, b, hd);
   bf16x8 qf[4], gf[4];
   uint4 uo[4];
 #pragma unroll
@@ -567,7 +407,7 @@ __global__ void __launch_bounds__(kT) attn_bwd_dq_kernel(AttnCoreParams P, AttnT
   // they are loaded and never used)
   const uint32_t* MW = P.mask + mask_word(bh, T / kKB, 0, hh, T, qok ? qi : 0);
   uint32_t wnext = DROP ? MW[0] : 0u;
-  const TileOff ko = tile_off(K.st, wave, lane), vo = tile_off(V.st, wave, lane);
+  const TileOff<kD> ko = tile_off<kD>(K.st, wave, lane), vo = tile_off<kD>(V.st, wave, lane);
   auto issue = [&](int it) {
     if (it >= nkb) return;
     char* base = lds + (it & 1) * 2 * kTile;
@@ -602,8 +442,8 @@ __global__ void __launch_bounds__(kT) attn_bwd_dq_kernel(AttnCoreParams P, AttnT
       f32x16 s = zero16(), dp = zero16();
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
-        s = mfma(row_rd(sK, 32 * kh + (lane & 31), 2 * ks + hh), qf[ks], s);
-        dp = mfma(row_rd(sV, 32 * kh + (lane & 31), 2 * ks + hh), gf[ks], dp);
+        s = mfma(row_rd<kD>(sK, 32 * kh + (lane & 31), 2 * ks + hh), qf[ks], s);
+        dp = mfma(row_rd<kD>(sV, 32 * kh + (lane & 31), 2 * ks + hh), gf[ks], dp);
       }
       const uint32_t wk = w >> (4 * kh);  // key 8g + 4hh + e of this half at bit 8e + g
       // causal mask only where this 32-key half reaches past the wave's first query
@@ -639,21 +479,13 @@ __global__ void __launch_bounds__(kT) attn_bwd_dq_kernel(AttnCoreParams P, AttnT
       for (int sg = 0; sg < 2; ++sg) {
         const bf16x8 df = acc_frag(s, sg);
 #pragma unroll
-        for (int dh = 0; dh < 2; ++dh) dacc[dh] = mfma(tr_op(sK, 32 * kh + 16 * sg, 32 * dh, lane), df, dacc[dh]);
+        for (int dh = 0; dh < 2; ++dh) dacc[dh] = mfma(tr_op<kD>(sK, 32 * kh + 16 * sg, 32 * dh, lane), df, dacc[dh]);
       }
     }
   }
   if (qok) {
     uint16_t* D = static_cast<uint16_t*>(dq.ptr) + b * dq.sb + hd * kD + static_cast<int64_t>(qi) * dq.st;
-    const float sc = P.scale;
-#pragma unroll
-    for (int dh = 0; dh < 2; ++dh)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int d0 = 32 * dh + 8 * g + 4 * hh;
-        *reinterpret_cast<uint2*>(D + d0) = make_uint2(pack2(dacc[dh][4 * g] * sc, dacc[dh][4 * g + 1] * sc),
-                                                       pack2(dacc[dh][4 * g + 2] * sc, dacc[dh][4 * g + 3] * sc));
-      }
+    store_row<kD>(D, dacc, P.scale, hh);
   }
 }
 
@@ -679,7 +511,7 @@ __global__ void __launch_bounds__(kT) attn_bwd_dkv_kernel(AttnCoreParams P, Attn
   const int kb0 = tile * 128;
   const int key = kb0 + wave * 32 + (lane & 31);  // this lane's key
   const bool kok = key < T;
-  const Ptrs Q = head(q, b, hd), K = head(k, b, hd), V = head(v, b, hd), G = head(dout, b, hd);
+  const Ptrs Q = head<kD>(q, b, hd), K = head<kD>(k, b, hd), V = head<kD>(v, b, hd), G = head<kD>(dout, b, hd);
   // key mask: the tile's two words (key blocks kb0/64 and, inside T, the next;
   // scalar loads); this wave's 32 keys are bits 32(wave&1)… of word wave>>1.
   // A hidden key's lane forces p = 0 for every query below: its dK / dV rows
@@ -732,7 +564,7 @@ __global__ void __launch_bounds__(kT) attn_bwd_dkv_kernel(AttnCoreParams P, Attn
   f32x16 dka[2] = {zero16(), zero16()}, dva[2] = {zero16(), zero16()};
   const int qt0 = CAUSAL ? kb0 / kKB : 0;  // first query tile that can see these keys
   const int nqt = T / kKB;
-  const TileOff qo = tile_off(Q.st, wave, lane), go = tile_off(G.st, wave, lane);
+  const TileOff<kD> qo = tile_off<kD>(Q.st, wave, lane), go = tile_off<kD>(G.st, wave, lane);
   auto issue = [&](int it) {
     if (qt0 + it >= nqt) return;
     const int qb = (qt0 + it) * kKB;
@@ -780,8 +612,8 @@ __global__ void __launch_bounds__(kT) attn_bwd_dkv_kernel(AttnCoreParams P, Attn
       dp[qs] = zero16();
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
-        s[qs] = mfma(row_rd(sQ, 32 * qs + (lane & 31), 2 * ks + hh), kf[ks], s[qs]);
-        dp[qs] = mfma(row_rd(sG, 32 * qs + (lane & 31), 2 * ks + hh), vf[ks], dp[qs]);
+        s[qs] = mfma(row_rd<kD>(sQ, 32 * qs + (lane & 31), 2 * ks + hh), kf[ks], s[qs]);
+        dp[qs] = mfma(row_rd<kD>(sG, 32 * qs + (lane & 31), 2 * ks + hh), vf[ks], dp[qs]);
       }
     }
 #pragma unroll
@@ -834,8 +666,8 @@ __global__ void __launch_bounds__(kT) attn_bwd_dkv_kernel(AttnCoreParams P, Attn
                                                                 pack2(dsv[4], dsv[5]), pack2(dsv[6], dsv[7])));
 #pragma unroll
         for (int dh = 0; dh < 2; ++dh) {
-          dva[dh] = mfma(tr_op(sG, 32 * qs + 16 * sg, 32 * dh, lane), pf, dva[dh]);
-          dka[dh] = mfma(tr_op(sQ, 32 * qs + 16 * sg, 32 * dh, lane), df, dka[dh]);
+          dva[dh] = mfma(tr_op<kD>(sG, 32 * qs + 16 * sg, 32 * dh, lane), pf, dva[dh]);
+          dka[dh] = mfma(tr_op<kD>(sQ, 32 * qs + 16 * sg, 32 * dh, lane), df, dka[dh]);
         }
       }
     }

@@ -1,41 +1,19 @@
 // Flash attention for head dim 128 on gfx950: forward, dQ and dK/dV kernels on
 // v_mfma_f32_32x32x16_bf16, bf16 I/O, fp32 online softmax, causal or not. No
 // dropout and no key-padding mask (those stay with the head-dim-64 kernels of
-// attention.hip, which this file does not touch).
+// attention.hip).
 //
-// What is shared with the head-dim-64 design (attention.hip's header has the
-// reasons): the "swapped" product Sᵀ = K·Qᵀ with one query (forward, dQ) or
-// one key (dK/dV) per lane, the accumulator used directly as the B operand of
-// the second product, v_permlane32_swap for the one cross-lane step of a row
-// reduction, K/V (or Q/dO) tiles of 64 rows arriving by global_load_lds into a
-// 2-deep ring with one barrier per tile, the FlashAttention-2 split of the
-// backward (no float atomics: two runs give the same bits) with δ = rowsum(dO
-// ∘ O) produced by the dQ kernel, and the causal serpentine work order.
+// The design shared with head dim 64 is in attn_mma.h, with its reasons: the
+// "swapped" product with one query (forward, dQ) or one key (dK/dV) per lane,
+// the accumulator as the B operand of the second product, the 2-deep DMA ring
+// of 64-row tiles, the FlashAttention-2 split of the backward with δ produced
+// by the dQ kernel, and the causal serpentine work order. The [64][128] tile
+// image, its swizzle and the bank argument for it are there too (swz<128>).
 //
-// What is new at 128:
+// What is particular to 128:
 //
-//  * LDS image. A tile is [64 rows][128 bf16]: 256-B rows, so EVERY row starts
-//    at bank 0 (64 banks × 4 B) and the head-dim-64 image (128-B rows, where
-//    the row's parity supplies one bit of the bank slot) no longer separates
-//    rows. 16-B chunk c (0 … 15) of row r lives at
-//        r·256 + 16·(c ^ swz(r)),   swz(r) = ((r & 3) << 2) | ((r >> 2) & 3)
-//    - row reads (ds_read_b128, served 16 lanes at a time: rows R … R+15, R a
-//      multiple of 16, one logical chunk c): swz is a bijection of r & 15 onto
-//      0 … 15, so the 16 lanes hit the 16 distinct 16-B slots of the 256-B
-//      bank image;
-//    - transposed reads (ds_read_b64_tr_b16, served 32 lanes at a time: rows
-//      R … R+3, R a multiple of 4, chunks C … C+3, C a multiple of 4, 8 B per
-//      lane): slot = (C ^ ((R >> 2) & 3)) ^ (j ^ (q << 2)) for chunk C + j of
-//      row R + q — j fills slot bits 0-1 and q slot bits 2-3, 16 distinct
-//      slots, each read as its two 8-B halves by two lanes: all 64 banks once.
-//    The plain r & 15 XOR would serve the row reads but put the four rows of a
-//    transposed read on the same four slots (a 4-way conflict); swapping the
-//    two bit pairs serves both.
 //  * DMA plan. A tile is 16 KiB = 16 wave-instructions of 1 KiB (4 rows each),
-//    4 per wave; the per-lane source offsets (row u/16 of the slab, swizzled
-//    chunk) are computed once per tensor (TileOff, 4 registers). Largest
-//    offset: (63·st + 15·8 + 7)·2 B with st < 2^24 elements (attn_view's
-//    check) is below 2^31, inside the 32-bit offset of the saddr form.
+//    4 per wave (TileOff<128>: 4 registers per tensor).
 //  * LDS budget. Forward and dQ: ring of 2 × (K | V) = 64 KiB, the static
 //    limit exactly. dK/dV: ring of 2 × (Q | dO | lse | δ) = 65 KiB, dynamic
 //    LDS (hipFuncAttributeMaxDynamicSharedMemorySize).
@@ -53,17 +31,13 @@
 
 #include <cmath>
 
-#include "attn_kernels.h"
-#include "bf16_vec.h"
+#include "attn_mma.h"
 
 namespace dcp {
 namespace kern {
 namespace {
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+using namespace attndev;  // fragments, tile image, DMA plan, work order (attn_mma.h)
 
 constexpr int kT = 256;
 constexpr int kD = 128;
@@ -75,170 +49,6 @@ constexpr int kStageKV = 2 * kTile;   // K | V (forward, dQ)
 constexpr int kStageQG = 2 * kTile + 2 * kKB * 4;  // Q | dO | lse | δ (dK/dV)
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kScale = 0.08838834764831845f;  // 1/sqrt(128), rounded once to fp32
-
-__device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) z[r] = 0.f;
-  return z;
-}
-// registers 8s … 8s+7 of an accumulator → bf16 operand fragment of k-step s
-__device__ __forceinline__ bf16x8 acc_frag(const f32x16& a, int s) {
-  const uint4 u = make_uint4(pack2(a[8 * s + 0], a[8 * s + 1]), pack2(a[8 * s + 2], a[8 * s + 3]),
-                             pack2(a[8 * s + 4], a[8 * s + 5]), pack2(a[8 * s + 6], a[8 * s + 7]));
-  return __builtin_bit_cast(bf16x8, u);
-}
-
-// ---- LDS tile image [64][128] bf16 (file header)
-__device__ __forceinline__ int swz(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
-__device__ __forceinline__ int img(int r, int c) { return r * 256 + 16 * (c ^ swz(r)); }
-
-__device__ __forceinline__ bf16x8 row_rd(const char* base, int r, int c) {
-  return *reinterpret_cast<const bf16x8*>(base + img(r, c));
-}
-
-// Operand A[x][row] = tile[row][x] for "A · X" with X an accumulator tile used
-// as the B operand: element j of lane l ↔ tile row rbase + 8(j>>2) + 4(l>>5) +
-// (j&3), column dcol0 + (l&31) — two ds_read_b64_tr_b16.
-__device__ __forceinline__ bf16x8 tr_op(const char* base, int rbase, int dcol0, int lane) {
-  const int g = lane >> 4, hh = lane >> 5, q = (lane >> 2) & 3, p = lane & 3;
-  const int c0 = dcol0 + 16 * (g & 1);
-  const int r0 = rbase + 4 * hh + q;
-  const int ch = (c0 >> 3) + (p >> 1);
-  const char* a0 = base + img(r0, ch) + 8 * (p & 1);
-  const char* a1 = base + img(r0 + 8, ch) + 8 * (p & 1);
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a0));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(a1));
-  const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, v);
-}
-
-// LDS DMA (16 / 4 B per lane) into the wave-uniform LDS address lds_dst (+
-// lane × size); wave-uniform 64-bit source base in SGPRs plus a 32-bit
-// per-lane byte offset. Inline asm so that the ring is ordered by the explicit
-// wait_vm0 + barrier at the top of each iteration only (a compiler-visible
-// global_load_lds makes hipcc wait for the NEXT tile's DMA before the first
-// LDS read after it). M0 is compiler-reserved: set and restored in-statement.
-__device__ __forceinline__ uint32_t lds_u32(const char* p) {
-  return __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(reinterpret_cast<uintptr_t>(p)));
-}
-__device__ __forceinline__ void glds16s(const void* sbase, uint32_t voff, char* lds_dst) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(sbase), "s"(lds_u32(lds_dst))
-               : "memory");
-}
-__device__ __forceinline__ void glds4s(const void* sbase, uint32_t voff, char* lds_dst) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(sbase), "s"(lds_u32(lds_dst))
-               : "memory");
-}
-__device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
-// DMA rows [r0, r0+64) of a strided [T][128] head slice into a tile image:
-// 4 waves × 4 wave-instructions of 1 KiB (4 rows each). TileOff: this lane's
-// byte offsets within the 64-row slab (row u / 16, swizzled chunk), computed
-// once per tensor; the slab base src + r0 · st is wave-uniform. The caller
-// keeps r0 + 64 <= T, so rows r0 … r0+63 and columns 0 … 127 of the head slice
-// are all that is read.
-struct TileOff {
-  uint32_t o[4];
-};
-__device__ __forceinline__ TileOff tile_off(int64_t st, int wave, int lane) {
-  TileOff t;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int u = (wave * 4 + j) * 64 + lane;  // 16-B unit of the image
-    const int r = u >> 4, lc = (u & 15) ^ swz(r);
-    t.o[j] = static_cast<uint32_t>((r * st + lc * 8) * 2);
-  }
-  return t;
-}
-__device__ __forceinline__ void stage_tile(const uint16_t* src, int64_t st, int r0, const TileOff& to, char* dst,
-                                           int wave) {
-  const uint16_t* base = src + static_cast<int64_t>(r0) * st;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) glds16s(base, to.o[j], dst + (wave * 4 + j) * 1024);
-}
-
-// combine x with the lane 32 apart: v_permlane32_swap (both results hold x
-// and its partner in some order; max / + are symmetric)
-__device__ __forceinline__ float max_xor32(float x) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float sum_xor32(float x) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-// (batch-head, tile) of this workgroup; causal: work items sorted heaviest
-// first, odd rounds of 256 launch positions reversed (serpentine), so every
-// CU's set of tiles sums to about the mean. heavy_last: the heaviest tile is
-// the last one (forward, dQ) or tile 0 (dK/dV). A bijection of the grid.
-__device__ __forceinline__ void attn_item(bool causal, bool heavy_last, int& bh, int& tile) {
-  const int nbh = static_cast<int>(gridDim.x), nt = static_cast<int>(gridDim.y);
-  if (!causal) {
-    bh = static_cast<int>(blockIdx.x);
-    tile = static_cast<int>(blockIdx.y);
-    return;
-  }
-  const int L = static_cast<int>(blockIdx.y) * nbh + static_cast<int>(blockIdx.x);
-  const int G = nbh * nt;
-  constexpr int C = 256;
-  const int r = L / C, pos = L % C;
-  int I = L;
-  if (r & 1) {
-    const int end = min(G, (r + 1) * C);  // a partial last round reverses within itself
-    I = end - 1 - pos;
-  }
-  bh = I % nbh;
-  const int rank = I / nbh;  // 0 = heaviest
-  tile = heavy_last ? nt - 1 - rank : rank;
-}
-
-struct Ptrs {
-  const uint16_t* p;
-  int64_t st;
-};
-__device__ __forceinline__ Ptrs head(const AttnTensor& t, int b, int hd) {
-  return Ptrs{static_cast<const uint16_t*>(t.ptr) + b * t.sb + hd * kD, t.st};
-}
-
-// this lane's row of a head slice as kKS operand fragments (columns 16ks +
-// 8hh … +7); a row past T is read at row 0 (in bounds) and selected to zero
-__device__ __forceinline__ void load_row(const Ptrs& X, int row, bool ok, int hh, bf16x8 (&f)[kKS]) {
-  const uint16_t* p = X.p + static_cast<int64_t>(ok ? row : 0) * X.st + 8 * hh;
-#pragma unroll
-  for (int ks = 0; ks < kKS; ++ks) {
-    const uint4 z = make_uint4(0, 0, 0, 0);
-    const uint4 u = *reinterpret_cast<const uint4*>(p + 16 * ks);
-    f[ks] = __builtin_bit_cast(bf16x8, ok ? u : z);
-  }
-}
-
-// acc[dh][4g + e] · sc → columns 32dh + 8g + 4hh + e of this lane's row
-__device__ __forceinline__ void store_row(uint16_t* row, const f32x16 (&acc)[kDH], float sc, int hh) {
-#pragma unroll
-  for (int dh = 0; dh < kDH; ++dh)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int d0 = 32 * dh + 8 * g + 4 * hh;
-      *reinterpret_cast<uint2*>(row + d0) = make_uint2(pack2(acc[dh][4 * g] * sc, acc[dh][4 * g + 1] * sc),
-                                                       pack2(acc[dh][4 * g + 2] * sc, acc[dh][4 * g + 3] * sc));
-    }
-}
 
 // ------------------------------------------------------------ forward ----
 // grid (B*H, ceil(T/128)); wave w of a workgroup owns queries tile·128 + 32w …
@@ -257,10 +67,10 @@ __global__ void __launch_bounds__(kT) attn128_fwd_kernel(Attn128Params P, AttnTe
   const int q0 = tile * 128 + wave * 32;  // this wave's first query
   const int qi = q0 + (lane & 31);        // this lane's query
   const bool qok = qi < T;
-  const Ptrs Q = head(q, b, hd), K = head(k, b, hd), V = head(v, b, hd);
+  const Ptrs Q = head<kD>(q, b, hd), K = head<kD>(k, b, hd), V = head<kD>(v, b, hd);
 
   bf16x8 qf[kKS];
-  load_row(Q, qi, qok, hh, qf);
+  load_row<kD>(Q, qi, qok, hh, qf);
   const float c = kScale * kLog2e;
 
   float m = -INFINITY, l = 0.f;
@@ -270,7 +80,7 @@ __global__ void __launch_bounds__(kT) attn128_fwd_kernel(Attn128Params P, AttnTe
   int nkb = T / kKB;
   if (CAUSAL) nkb = min(nkb, 2 * tile + 2);
 
-  const TileOff ko = tile_off(K.st, wave, lane), vo = tile_off(V.st, wave, lane);
+  const TileOff<kD> ko = tile_off<kD>(K.st, wave, lane), vo = tile_off<kD>(V.st, wave, lane);
   auto issue = [&](int it) {
     if (it >= nkb) return;
     char* base = lds + (it & 1) * kStageKV;
@@ -294,7 +104,7 @@ __global__ void __launch_bounds__(kT) attn128_fwd_kernel(Attn128Params P, AttnTe
     for (int kh = 0; kh < 2; ++kh) {
       s[kh] = zero16();
 #pragma unroll
-      for (int ks = 0; ks < kKS; ++ks) s[kh] = mfma(row_rd(sK, 32 * kh + (lane & 31), 2 * ks + hh), qf[ks], s[kh]);
+      for (int ks = 0; ks < kKS; ++ks) s[kh] = mfma(row_rd<kD>(sK, 32 * kh + (lane & 31), 2 * ks + hh), qf[ks], s[kh]);
     }
     // s[kh][r]: key kb + 32kh + (r&3) + 8(r>>2) + 4hh, query qi. Raw scores:
     // the max is taken before scaling (c > 0), the scale rides in the
@@ -340,12 +150,12 @@ __global__ void __launch_bounds__(kT) attn128_fwd_kernel(Attn128Params P, AttnTe
       for (int sg = 0; sg < 2; ++sg) {
         const bf16x8 pf = acc_frag(s[kh], sg);
 #pragma unroll
-        for (int dh = 0; dh < kDH; ++dh) oacc[dh] = mfma(tr_op(sV, 32 * kh + 16 * sg, 32 * dh, lane), pf, oacc[dh]);
+        for (int dh = 0; dh < kDH; ++dh) oacc[dh] = mfma(tr_op<kD>(sV, 32 * kh + 16 * sg, 32 * dh, lane), pf, oacc[dh]);
       }
   }
   if (qok) {
     uint16_t* O = static_cast<uint16_t*>(o.ptr) + b * o.sb + hd * kD + static_cast<int64_t>(qi) * o.st;
-    store_row(O, oacc, 1.f / l, hh);
+    store_row<kD>(O, oacc, 1.f / l, hh);
     if (hh == 0) lse[static_cast<int64_t>(bh) * T + qi] = m * c + log2f(l);
   }
 }
@@ -371,10 +181,11 @@ __global__ void __launch_bounds__(kT) attn128_bwd_dq_kernel(Attn128Params P, Att
   const int q0 = tile * 128 + wave * 32;
   const int qi = q0 + (lane & 31);
   const bool qok = qi < T;
-  const Ptrs Q = head(q, b, hd), K = head(k, b, hd), V = head(v, b, hd), G = head(dout, b, hd), O = head(o, b, hd);
+  const Ptrs Q = head<kD>(q, b, hd), K = head<kD>(k, b, hd), V = head<kD>(v, b, hd), G = head<kD>(dout, b, hd),
+             O = head<kD>(o, b, hd);
   bf16x8 qf[kKS], gf[kKS];
-  load_row(Q, qi, qok, hh, qf);
-  load_row(G, qi, qok, hh, gf);
+  load_row<kD>(Q, qi, qok, hh, qf);
+  load_row<kD>(G, qi, qok, hh, gf);
   float dpart = 0.f;  // this lane's half of the row's 128 products (lanes l, l + 32: one row)
   {
     const uint16_t* po = O.p + static_cast<int64_t>(qok ? qi : 0) * O.st + 8 * hh;
@@ -400,7 +211,7 @@ __global__ void __launch_bounds__(kT) attn128_bwd_dq_kernel(Attn128Params P, Att
   for (int dh = 0; dh < kDH; ++dh) dacc[dh] = zero16();
   int nkb = T / kKB;
   if (CAUSAL) nkb = min(nkb, 2 * tile + 2);
-  const TileOff ko = tile_off(K.st, wave, lane), vo = tile_off(V.st, wave, lane);
+  const TileOff<kD> ko = tile_off<kD>(K.st, wave, lane), vo = tile_off<kD>(V.st, wave, lane);
   auto issue = [&](int it) {
     if (it >= nkb) return;
     char* base = lds + (it & 1) * kStageKV;
@@ -423,8 +234,8 @@ __global__ void __launch_bounds__(kT) attn128_bwd_dq_kernel(Attn128Params P, Att
       f32x16 s = zero16(), dp = zero16();
 #pragma unroll
       for (int ks = 0; ks < kKS; ++ks) {
-        s = mfma(row_rd(sK, 32 * kh + (lane & 31), 2 * ks + hh), qf[ks], s);
-        dp = mfma(row_rd(sV, 32 * kh + (lane & 31), 2 * ks + hh), gf[ks], dp);
+        s = mfma(row_rd<kD>(sK, 32 * kh + (lane & 31), 2 * ks + hh), qf[ks], s);
+        dp = mfma(row_rd<kD>(sV, 32 * kh + (lane & 31), 2 * ks + hh), gf[ks], dp);
       }
       // causal mask only where this 32-key half reaches past the wave's first query
       const bool diag = CAUSAL && kb + 32 * kh + 31 > q0;
@@ -439,13 +250,13 @@ __global__ void __launch_bounds__(kT) attn128_bwd_dq_kernel(Attn128Params P, Att
       for (int sg = 0; sg < 2; ++sg) {
         const bf16x8 df = acc_frag(s, sg);
 #pragma unroll
-        for (int dh = 0; dh < kDH; ++dh) dacc[dh] = mfma(tr_op(sK, 32 * kh + 16 * sg, 32 * dh, lane), df, dacc[dh]);
+        for (int dh = 0; dh < kDH; ++dh) dacc[dh] = mfma(tr_op<kD>(sK, 32 * kh + 16 * sg, 32 * dh, lane), df, dacc[dh]);
       }
     }
   }
   if (qok) {
     uint16_t* D = static_cast<uint16_t*>(dq.ptr) + b * dq.sb + hd * kD + static_cast<int64_t>(qi) * dq.st;
-    store_row(D, dacc, kScale, hh);
+    store_row<kD>(D, dacc, kScale, hh);
   }
 }
 
@@ -472,10 +283,10 @@ __global__ void __launch_bounds__(kT) attn128_bwd_dkv_kernel(Attn128Params P, At
   const int k0 = kb0 + wave * 32;    // this wave's first key
   const int key = k0 + (lane & 31);  // this lane's key
   const bool kok = key < T;
-  const Ptrs Q = head(q, b, hd), K = head(k, b, hd), V = head(v, b, hd), G = head(dout, b, hd);
+  const Ptrs Q = head<kD>(q, b, hd), K = head<kD>(k, b, hd), V = head<kD>(v, b, hd), G = head<kD>(dout, b, hd);
   bf16x8 kf[kKS], vf[kKS];
-  load_row(K, key, kok, hh, kf);
-  load_row(V, key, kok, hh, vf);
+  load_row<kD>(K, key, kok, hh, kf);
+  load_row<kD>(V, key, kok, hh, vf);
   const float c = kScale * kLog2e;
   const float* L = lse + static_cast<int64_t>(bh) * T;
   const float* DL = delta + static_cast<int64_t>(bh) * T;
@@ -488,7 +299,7 @@ __global__ void __launch_bounds__(kT) attn128_bwd_dkv_kernel(Attn128Params P, At
   }
   const int qt0 = CAUSAL ? kb0 / kKB : 0;  // first query tile that can see these keys (kb0 < T: qt0 < nqt)
   const int nqt = T / kKB;
-  const TileOff qo = tile_off(Q.st, wave, lane), go = tile_off(G.st, wave, lane);
+  const TileOff<kD> qo = tile_off<kD>(Q.st, wave, lane), go = tile_off<kD>(G.st, wave, lane);
   auto issue = [&](int it) {
     if (qt0 + it >= nqt) return;
     const int qb = (qt0 + it) * kKB;  // qb + 64 <= T
@@ -518,8 +329,8 @@ __global__ void __launch_bounds__(kT) attn128_bwd_dkv_kernel(Attn128Params P, At
       f32x16 s = zero16(), dp = zero16();
 #pragma unroll
       for (int ks = 0; ks < kKS; ++ks) {
-        s = mfma(row_rd(sQ, 32 * qs + (lane & 31), 2 * ks + hh), kf[ks], s);
-        dp = mfma(row_rd(sG, 32 * qs + (lane & 31), 2 * ks + hh), vf[ks], dp);
+        s = mfma(row_rd<kD>(sQ, 32 * qs + (lane & 31), 2 * ks + hh), kf[ks], s);
+        dp = mfma(row_rd<kD>(sG, 32 * qs + (lane & 31), 2 * ks + hh), vf[ks], dp);
       }
       // the mask only where some query of the slice precedes the wave's last key
       const bool diag = CAUSAL && qb + 32 * qs < k0 + 31;
@@ -545,8 +356,8 @@ __global__ void __launch_bounds__(kT) attn128_bwd_dkv_kernel(Attn128Params P, At
         const bf16x8 pf = acc_frag(s, sg), df = acc_frag(dp, sg);
 #pragma unroll
         for (int dh = 0; dh < kDH; ++dh) {
-          dva[dh] = mfma(tr_op(sG, 32 * qs + 16 * sg, 32 * dh, lane), pf, dva[dh]);
-          dka[dh] = mfma(tr_op(sQ, 32 * qs + 16 * sg, 32 * dh, lane), df, dka[dh]);
+          dva[dh] = mfma(tr_op<kD>(sG, 32 * qs + 16 * sg, 32 * dh, lane), pf, dva[dh]);
+          dka[dh] = mfma(tr_op<kD>(sQ, 32 * qs + 16 * sg, 32 * dh, lane), df, dka[dh]);
         }
       }
     }
@@ -554,8 +365,8 @@ __global__ void __launch_bounds__(kT) attn128_bwd_dkv_kernel(Attn128Params P, At
   if (kok) {
     uint16_t* DK = static_cast<uint16_t*>(dk.ptr) + b * dk.sb + hd * kD + static_cast<int64_t>(key) * dk.st;
     uint16_t* DV = static_cast<uint16_t*>(dv.ptr) + b * dv.sb + hd * kD + static_cast<int64_t>(key) * dv.st;
-    store_row(DK, dka, kScale, hh);
-    store_row(DV, dva, 1.f, hh);
+    store_row<kD>(DK, dka, kScale, hh);
+    store_row<kD>(DV, dva, 1.f, hh);
   }
 }
 

@@ -1,7 +1,7 @@
 // Device helpers shared by the fp8 kernels (gemm_fp8.hip, gemm_fp8_wgrad.hip):
 // the fp8 cast, the 128 x 128 x 128 tile constants, the swizzled LDS image and
-// its fragment read, the LDS DMA and the ring's ordering primitives.
-// gemm_fp8.hip's header has the image and DMA arguments.
+// its fragment read; the LDS DMA and the ring's ordering primitives come from
+// lds_dma.h. gemm_fp8.hip's header has the image and DMA arguments.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,6 +9,7 @@
 #include <cstdint>
 
 #include "fp8_kernels.h"
+#include "lds_dma.h"
 
 namespace dcp {
 namespace kern {
@@ -50,27 +51,9 @@ constexpr int kUnit = 0x7f7f7f7f;  // E8M0 1.0 in every byte: unit block scales
 
 __device__ __forceinline__ int swz(int r) { return (r >> 1) & 7; }
 
-// LDS DMA, 16 B per lane, into the wave-uniform LDS address lds_dst (+ 16 ·
-// lane): wave-uniform 64-bit source base in SGPRs plus a 32-bit per-lane byte
-// offset. Inline asm, so the ring is ordered by the explicit vmcnt(0) +
-// barrier of each iteration only (attention_d128.hip has the reasons). M0 is
-// compiler-reserved: set and restored in-statement.
-__device__ __forceinline__ uint32_t lds_u32(const char* p) {
-  return __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(reinterpret_cast<uintptr_t>(p)));
-}
-__device__ __forceinline__ void glds16s(const void* sbase, uint32_t voff, char* lds_dst) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(sbase), "s"(lds_u32(lds_dst))
-               : "memory");
-}
-__device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
+// the LDS DMA (glds16s) and the ring's ordering primitives (wait_vm0, barrier):
+// lds_dma.h, which has the reasons for their form
+using namespace ldsdma;
 
 // this lane's 32-byte K-run of MFMA k-step s: row r, chunks 4 s + 2 hh, + 1
 __device__ __forceinline__ i32x8 frag(const char* img, int r, int s, int hh) {

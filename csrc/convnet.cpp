@@ -50,7 +50,7 @@ std::vector<at::Tensor> fwd(const at::Tensor& x_in, const at::Tensor& w1, const 
   if (drop_p > 0.0) {
     DK_CHECK(drop_p < 1.0, "convnet_features_fwd: dropout p must be < 1");
     d.thr = kern::dropout_threshold(static_cast<float>(drop_p));
-    d.scale = static_cast<float>(1.0 / (1.0 - drop_p));
+    d.scale = kern::dropout_scale(drop_p);
     d.seed = static_cast<uint64_t>(seed);
     if (offset_dev.has_value() && offset_dev->defined()) d.offset_dev = offset_dev->data_ptr<int64_t>();
   }

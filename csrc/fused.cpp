@@ -1624,7 +1624,7 @@ namespace {
 kern::LnDropAdd ln_drop(double p, int64_t seed, const c10::optional<at::Tensor>& offset_dev) {
   kern::LnDropAdd da{};
   da.thr = kern::dropout_threshold(static_cast<float>(p));
-  da.scale = p < 1.0 ? 1.f / (1.f - static_cast<float>(p)) : 0.f;
+  da.scale = kern::dropout_scale(p);
   da.seed = static_cast<uint64_t>(seed);
   da.offset = 0;
   da.offset_dev = offset_dev.has_value() && offset_dev->defined() ? offset_dev->data_ptr<int64_t>() : nullptr;
@@ -1835,7 +1835,7 @@ at::Tensor dropout_fwd(const at::Tensor& x, const c10::optional<at::Tensor>& res
   }
   at::Tensor y = at::empty_like(x, x.options().dtype(yt));
   kern::dropout(dr_dtype(x), dr_dtype(y), x.data_ptr(), res.defined() ? res.data_ptr() : nullptr, y.data_ptr(),
-                x.numel(), static_cast<float>(p), static_cast<uint64_t>(seed), static_cast<uint64_t>(offset),
+                x.numel(), p, static_cast<uint64_t>(seed), static_cast<uint64_t>(offset),
                 offset_dev.has_value() && offset_dev->defined() ? offset_dev->data_ptr<int64_t>() : nullptr,
                 stream_of(x));
   return y;
@@ -1848,7 +1848,7 @@ at::Tensor feature_dropout_fwd(const at::Tensor& x, double p, int64_t seed, int6
   const int64_t rows = x.size(0) * x.size(1);
   at::Tensor y = at::empty_like(x);
   kern::feature_dropout(dr_dtype(x), x.data_ptr(), y.data_ptr(), rows, rows ? x.numel() / rows : 0,
-                        static_cast<float>(p), static_cast<uint64_t>(seed), static_cast<uint64_t>(offset),
+                        p, static_cast<uint64_t>(seed), static_cast<uint64_t>(offset),
                         offset_dev.has_value() && offset_dev->defined() ? offset_dev->data_ptr<int64_t>() : nullptr,
                         stream_of(x));
   return y;
@@ -1883,7 +1883,7 @@ kern::PoolEpi pool_epi(bool relu, double drop_p, int64_t seed, const c10::option
   if (drop_p > 0.0) {
     DK_CHECK(drop_p < 1.0, "fused pool: dropout p must be < 1");
     e.thr = kern::dropout_threshold(static_cast<float>(drop_p));
-    e.scale = static_cast<float>(1.0 / (1.0 - drop_p));
+    e.scale = kern::dropout_scale(drop_p);
     e.seed = static_cast<uint64_t>(seed);
     if (offset_dev.has_value() && offset_dev->defined()) e.offset_dev = offset_dev->data_ptr<int64_t>();
   }

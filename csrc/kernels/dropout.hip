@@ -145,11 +145,13 @@ uint32_t dropout_threshold(float p) {
   return t >= 4294967295.0 ? 0xFFFFFFFFu : static_cast<uint32_t>(t);
 }
 
-void dropout(int xdtype, int ydtype, const void* x, const void* res, void* y, int64_t n, float p, uint64_t seed,
+float dropout_scale(double p) { return p < 1.0 ? static_cast<float>(1.0 / (1.0 - p)) : 0.f; }
+
+void dropout(int xdtype, int ydtype, const void* x, const void* res, void* y, int64_t n, double p, uint64_t seed,
              uint64_t offset, const int64_t* offset_dev, hipStream_t s) {
   if (n <= 0) return;
-  const uint32_t thr = dropout_threshold(p);
-  const float scale = p < 1.f ? 1.f / (1.f - p) : 0.f;
+  const uint32_t thr = dropout_threshold(static_cast<float>(p));
+  const float scale = dropout_scale(p);
   const dim3 g = grid_for((n + 3) / 4);
 #define DK_DR(XD, RD, R) \
   hipLaunchKernelGGL((dropout_kernel<XD, RD, R>), g, dim3(kT), 0, s, x, res, y, n, thr, scale, seed, offset, \
@@ -166,11 +168,11 @@ void dropout(int xdtype, int ydtype, const void* x, const void* res, void* y, in
 #undef DK_DR
 }
 
-void feature_dropout(int dtype, const void* x, void* y, int64_t rows, int64_t inner, float p, uint64_t seed,
+void feature_dropout(int dtype, const void* x, void* y, int64_t rows, int64_t inner, double p, uint64_t seed,
                      uint64_t offset, const int64_t* offset_dev, hipStream_t s) {
   if (rows <= 0) return;
-  const uint32_t thr = dropout_threshold(p);
-  const float scale = p < 1.f ? 1.f / (1.f - p) : 0.f;
+  const uint32_t thr = dropout_threshold(static_cast<float>(p));
+  const float scale = dropout_scale(p);
   const dim3 g(static_cast<unsigned>(rows < 65535 ? rows : 65535));
   if (dtype == DR_BF16)
     hipLaunchKernelGGL(feature_dropout_kernel<DR_BF16>, g, dim3(kT), 0, s, x, y, rows, inner, thr, scale, seed, offset,

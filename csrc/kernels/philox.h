@@ -32,7 +32,8 @@ __device__ __forceinline__ U4 philox(uint64_t seed, uint64_t counter) {
   return U4{c0, c1, c2, c3};
 }
 
-// keep iff uniform(0,1] >= p  ⇔  u32 >= p * 2^32 (threshold precomputed)
+// keep iff the raw word r >= thr, thr = min(floor(float(p) * 2^32), 0xFFFFFFFF)
+// (dropout_threshold, precomputed on the host): P(keep) = 1 - thr / 2^32
 __device__ __forceinline__ bool keep(uint32_t r, uint32_t thr) { return r >= thr; }
 
 // lane `i & 3` of the Philox block holding row i (rows grouped 4 per counter)

@@ -1,13 +1,14 @@
 // Torch wrappers + bindings of the head-dim-128 flash attention kernels
 // (kernels/attention_d128.hip): bf16 [B, T, H*128] views with unit last stride
 // (slices of one packed [B, T, 3C] projection are read and written in place),
-// causal or not, no dropout, no key-padding mask. Kernel launches on the
-// current stream only: no host sync, no memset / memcpy (graph-capturable).
+// causal or not, optionally with a sliding window on the causal mask, no
+// dropout, no key-padding mask. Kernel launches on the current stream only: no host sync, no memset / memcpy (graph-capturable).
 #include <torch/extension.h>
 
 #include <c10/hip/HIPGuard.h>
 #include <c10/hip/HIPStream.h>
 
+#include <algorithm>
 #include <initializer_list>
 
 #include "common.h"
@@ -39,14 +40,18 @@ kern::AttnOut out_view(const at::Tensor& t, const at::Tensor& q, const char* wha
   return kern::AttnOut{t.data_ptr(), v.sb, v.st};
 }
 
-kern::Attn128Params params(const at::Tensor& q, int64_t heads, bool causal) {
+kern::Attn128Params params(const at::Tensor& q, int64_t heads, bool causal, int64_t window) {
   DK_CHECK(q.dim() == 3, "attention (head dim 128): [B, T, H*128] tensors required");
   const int64_t B = q.size(0), T = q.size(1), C = q.size(2);
   DK_CHECK(heads > 0 && C == heads * 128, "attention (head dim 128): last dim must be heads * 128");
   DK_CHECK(kern::attn128_supported(static_cast<int>(T)) && T <= 8192,
            "attention (head dim 128): sequence length must be a multiple of 64, at most 8192");
   DK_CHECK(B > 0 && B * heads < (int64_t(1) << 31) / 64, "attention (head dim 128): batch * heads out of range");
-  return kern::Attn128Params{static_cast<int>(B), static_cast<int>(heads), static_cast<int>(T), causal};
+  DK_CHECK(window >= 0, "attention (head dim 128): window must be >= 1, or 0 for none");
+  DK_CHECK(window == 0 || causal, "attention (head dim 128): a window requires causal");
+  // any window >= T is plain causal attention: T stands for all of them
+  return kern::Attn128Params{static_cast<int>(B), static_cast<int>(heads), static_cast<int>(T), causal,
+                             static_cast<int>(std::min(window, T))};
 }
 
 }  // namespace
@@ -57,8 +62,8 @@ bool attn128_ok(int64_t T, int64_t C, int64_t heads) {
 
 // o [B, T, H*128] (contiguous), lse [B*H, T] fp32 (log2 domain, for the backward)
 std::vector<at::Tensor> flash_attn128_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
-                                          int64_t heads, bool causal) {
-  const kern::Attn128Params p = params(q, heads, causal);
+                                          int64_t heads, bool causal, int64_t window) {
+  const kern::Attn128Params p = params(q, heads, causal, window);
   const kern::AttnTensor vq = view(q, q, "flash_attn128_fwd: q"), vk = view(k, q, "flash_attn128_fwd: k"),
                          vv = view(v, q, "flash_attn128_fwd: v");
   c10::hip::HIPGuard guard(q.device().index());
@@ -71,8 +76,8 @@ std::vector<at::Tensor> flash_attn128_fwd(const at::Tensor& q, const at::Tensor&
 // writes dq, dk, dv (strided views allowed, e.g. slices of one packed buffer)
 void flash_attn128_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                        const at::Tensor& o, const at::Tensor& lse, int64_t heads, bool causal, at::Tensor& dq,
-                       at::Tensor& dk, at::Tensor& dv) {
-  const kern::Attn128Params p = params(q, heads, causal);
+                       at::Tensor& dk, at::Tensor& dv, int64_t window) {
+  const kern::Attn128Params p = params(q, heads, causal, window);
   DK_CHECK(lse.is_cuda() && lse.device() == q.device() && lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
                lse.numel() == q.size(0) * heads * q.size(1),
            "flash_attn128_bwd: lse must be the forward's fp32 [B*H, T] tensor");
@@ -92,10 +97,10 @@ void bind(pybind11::module& m) {
   namespace py = pybind11;
   m.def("attn128_ok", &attn128_ok);
   m.def("flash_attn128_fwd", &flash_attn128_fwd, "MFMA flash attention forward (head dim 128) -> (o, lse)",
-        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("heads"), py::arg("causal"));
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("heads"), py::arg("causal"), py::arg("window") = 0);
   m.def("flash_attn128_bwd", &flash_attn128_bwd, "MFMA flash attention backward (head dim 128) into dq/dk/dv",
         py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("lse"), py::arg("heads"),
-        py::arg("causal"), py::arg("dq"), py::arg("dk"), py::arg("dv"));
+        py::arg("causal"), py::arg("dq"), py::arg("dk"), py::arg("dv"), py::arg("window") = 0);
 }
 
 }  // namespace attn128

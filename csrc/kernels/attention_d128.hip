@@ -27,6 +27,23 @@
 //    32 MFMAs) and stream Q/dO twice, 1.5× the matrix work and 2× the DMA, to
 //    buy occupancy that the 65-KiB stage already limits to two workgroups per
 //    CU. NOTES §44 has the resource table the compiler reports.
+//
+// Sliding window (WIN, with CAUSAL only; NOTES §49). Query i attends key j iff
+// i − W < j ≤ i, W = Attn128Params::window at run time (0 < W < T: the launch
+// functions route everything else to the kernels without window code). The
+// band has a second edge, so each kernel gets what the causal edge already
+// has, mirrored:
+//
+//  * a bound of the streamed range: forward and dQ start at the first 64-key
+//    block that some query of the 128-query tile can see (it_lo) — the blocks
+//    below are never staged; dK/dV ends its query stream after the last tile
+//    that can see some key of the 128-key tile;
+//  * a wave-uniform skip of staged blocks (32-row sub-tiles in dK/dV) that lie
+//    wholly outside the band of this wave's 32 rows;
+//  * an elementwise mask on the blocks the edge crosses, and only there.
+//
+// Tile geometry, LDS image, DMA ring and launch bounds are those of the causal
+// kernels. The forward's running max needs one more step (there).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -53,7 +70,7 @@ constexpr float kScale = 0.08838834764831845f;  // 1/sqrt(128), rounded once to 
 // ------------------------------------------------------------ forward ----
 // grid (B*H, ceil(T/128)); wave w of a workgroup owns queries tile·128 + 32w …
 // +31, one per lane pair (l, l + 32: the two halves of each 16-wide k-step).
-template <bool CAUSAL>
+template <bool CAUSAL, bool WIN = false>
 __global__ void __launch_bounds__(kT) attn128_fwd_kernel(Attn128Params P, AttnTensor q, AttnTensor k, AttnTensor v,
                                                          AttnOut o, float* __restrict__ lse) {
   __shared__ __attribute__((aligned(16))) char lds[2 * kStageKV];  // [ring][K | V]: 64 KiB
@@ -79,6 +96,11 @@ __global__ void __launch_bounds__(kT) attn128_fwd_kernel(Attn128Params P, AttnTe
   for (int dh = 0; dh < kDH; ++dh) oacc[dh] = zero16();
   int nkb = T / kKB;
   if (CAUSAL) nkb = min(nkb, 2 * tile + 2);
+  // window: the first block that some query of the tile sees, i.e. the one
+  // with key 128·tile − W + 1 of the tile's first query (it_lo ≤ 2·tile < nkb).
+  // The ring slot stays it & 1 in issue and consumer alike, whatever it_lo.
+  const int W = WIN ? P.window : 0;
+  const int it_lo = WIN ? max(0, 128 * tile - W + 1) / kKB : 0;
 
   const TileOff<kD> ko = tile_off<kD>(K.st, wave, lane), vo = tile_off<kD>(V.st, wave, lane);
   auto issue = [&](int it) {
@@ -87,8 +109,8 @@ __global__ void __launch_bounds__(kT) attn128_fwd_kernel(Attn128Params P, AttnTe
     stage_tile(K.p, K.st, it * kKB, ko, base, wave);
     stage_tile(V.p, V.st, it * kKB, vo, base + kTile, wave);
   };
-  issue(0);
-  for (int it = 0; it < nkb; ++it) {
+  issue(it_lo);
+  for (int it = it_lo; it < nkb; ++it) {
     wait_vm0();
     barrier();
     issue(it + 1);
@@ -99,6 +121,8 @@ __global__ void __launch_bounds__(kT) attn128_fwd_kernel(Attn128Params P, AttnTe
     // a key block wholly after this wave's last query: DMA and barrier only
     if (q0 >= T) continue;
     if (CAUSAL && kb > q0 + 31) continue;
+    // (window) or wholly below the first query's lowest key, hence below every query's
+    if (WIN && kb + kKB - 1 < q0 - W + 1) continue;
     f32x16 s[2];
 #pragma unroll
     for (int kh = 0; kh < 2; ++kh) {
@@ -119,14 +143,35 @@ __global__ void __launch_bounds__(kT) attn128_fwd_kernel(Attn128Params P, AttnTe
           s[kh][r] = key > qi ? -INFINITY : s[kh][r];
         }
     }
+    // the window's lower edge, only on blocks that reach below the lowest key
+    // of the wave's last query (with W < 64 a block can take both masks)
+    if (WIN && kb <= q0 + 31 - W) {
+#pragma unroll
+      for (int kh = 0; kh < 2; ++kh)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int key = kb + 32 * kh + (r & 3) + 8 * (r >> 2) + 4 * hh;
+          s[kh][r] = key <= qi - W ? -INFINITY : s[kh][r];
+        }
+    }
     float mx = m;
 #pragma unroll
     for (int kh = 0; kh < 2; ++kh)
 #pragma unroll
       for (int r = 0; r < 16; r += 2) mx = fmaxf(mx, fmaxf(s[kh][r], s[kh][r + 1]));
-    mx = max_xor32(mx);  // finite: every wave's first block holds key 0 <= its queries
-    const float alpha = __builtin_amdgcn_exp2f((m - mx) * c);
-    const float nmc = -mx * c;
+    mx = max_xor32(mx);
+    // Without a window mx is finite: every wave's first block holds key 0 <= its
+    // queries. With one, a wave's first block is visible to its first query but
+    // can be wholly hidden from a later one (T 128, W 64, q0 96: block [0, 63]
+    // holds key 63 for queries 96…126 and nothing for 127), and that row has
+    // mx = m = -inf. Its exponents are then taken against 0, as in
+    // attention.hip's key-mask forward: alpha and every p are exp2(-inf) = 0,
+    // never (-inf) - (-inf); l stays 0 and O untouched until the row's first
+    // visible key. A row's own key is always visible, so the final l > 0.
+    float mxs = mx;
+    if (WIN) mxs = mx == -INFINITY ? 0.f : mx;
+    const float alpha = __builtin_amdgcn_exp2f((m - mxs) * c);
+    const float nmc = -mxs * c;
     float rs = 0.f;
 #pragma unroll
     for (int kh = 0; kh < 2; ++kh)
@@ -165,7 +210,7 @@ __global__ void __launch_bounds__(kT) attn128_fwd_kernel(Attn128Params P, AttnTe
 // dSᵀ = Pᵀ∘(dPᵀ − δ), dQᵀ += Kᵀ·dSᵀ. δ = rowsum(dO ∘ O) is computed here from
 // the query rows' dO (already loaded) and O, and stored for the dK/dV kernel,
 // which runs after this one.
-template <bool CAUSAL>
+template <bool CAUSAL, bool WIN = false>
 __global__ void __launch_bounds__(kT) attn128_bwd_dq_kernel(Attn128Params P, AttnTensor q, AttnTensor k,
                                                             AttnTensor v, AttnTensor dout, AttnTensor o,
                                                             const float* __restrict__ lse,
@@ -211,6 +256,10 @@ __global__ void __launch_bounds__(kT) attn128_bwd_dq_kernel(Attn128Params P, Att
   for (int dh = 0; dh < kDH; ++dh) dacc[dh] = zero16();
   int nkb = T / kKB;
   if (CAUSAL) nkb = min(nkb, 2 * tile + 2);
+  // window: the forward's block range, skip and lower-edge mask. No guard of
+  // the exponent here: p is taken against the stored lse, which is finite.
+  const int W = WIN ? P.window : 0;
+  const int it_lo = WIN ? max(0, 128 * tile - W + 1) / kKB : 0;
   const TileOff<kD> ko = tile_off<kD>(K.st, wave, lane), vo = tile_off<kD>(V.st, wave, lane);
   auto issue = [&](int it) {
     if (it >= nkb) return;
@@ -218,8 +267,8 @@ __global__ void __launch_bounds__(kT) attn128_bwd_dq_kernel(Attn128Params P, Att
     stage_tile(K.p, K.st, it * kKB, ko, base, wave);
     stage_tile(V.p, V.st, it * kKB, vo, base + kTile, wave);
   };
-  issue(0);
-  for (int it = 0; it < nkb; ++it) {
+  issue(it_lo);
+  for (int it = it_lo; it < nkb; ++it) {
     wait_vm0();
     barrier();
     issue(it + 1);
@@ -228,9 +277,12 @@ __global__ void __launch_bounds__(kT) attn128_bwd_dq_kernel(Attn128Params P, Att
     const int kb = it * kKB;
     if (q0 >= T) continue;
     if (CAUSAL && kb > q0 + 31) continue;
+    if (WIN && kb + kKB - 1 < q0 - W + 1) continue;  // wholly below every query's lowest key
     // one 32-key half at a time (32 live accumulator registers, not 64)
 #pragma unroll 1
     for (int kh = 0; kh < 2; ++kh) {
+      // (window) a half wholly outside the band of the wave's queries adds nothing
+      if (WIN && (kb + 32 * kh + 31 < q0 - W + 1 || kb + 32 * kh > q0 + 31)) continue;
       f32x16 s = zero16(), dp = zero16();
 #pragma unroll
       for (int ks = 0; ks < kKS; ++ks) {
@@ -239,11 +291,14 @@ __global__ void __launch_bounds__(kT) attn128_bwd_dq_kernel(Attn128Params P, Att
       }
       // causal mask only where this 32-key half reaches past the wave's first query
       const bool diag = CAUSAL && kb + 32 * kh + 31 > q0;
+      // and the window's where it reaches below the last query's lowest key
+      const bool low = WIN && kb + 32 * kh <= q0 + 31 - W;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int key = kb + 32 * kh + (r & 3) + 8 * (r >> 2) + 4 * hh;
         float p = __builtin_amdgcn_exp2f(fmaf(s[r], c, -lse2));
         if (CAUSAL && diag) p = key > qi ? 0.f : p;
+        if (WIN && low) p = key <= qi - W ? 0.f : p;
         s[r] = p * (dp[r] - dlt);  // dSᵀ (without the softmax scale)
       }
 #pragma unroll
@@ -265,7 +320,7 @@ __global__ void __launch_bounds__(kT) attn128_bwd_dq_kernel(Attn128Params P, Att
 // dVᵀ += dOᵀ·P, dKᵀ += Qᵀ·dS. Q / dO tiles (+ lse, δ) stream through LDS; each
 // wave keeps its 32 keys' dKᵀ, dVᵀ over all 128 columns in registers (file
 // header: one pass, one 32-query sub-tile in flight).
-template <bool CAUSAL>
+template <bool CAUSAL, bool WIN = false>
 __global__ void __launch_bounds__(kT) attn128_bwd_dkv_kernel(Attn128Params P, AttnTensor q, AttnTensor k,
                                                              AttnTensor v, AttnTensor dout,
                                                              const float* __restrict__ lse,
@@ -298,7 +353,12 @@ __global__ void __launch_bounds__(kT) attn128_bwd_dkv_kernel(Attn128Params P, At
     dva[dh] = zero16();
   }
   const int qt0 = CAUSAL ? kb0 / kKB : 0;  // first query tile that can see these keys (kb0 < T: qt0 < nqt)
-  const int nqt = T / kKB;
+  int nqt = T / kKB;
+  // window: the last query that sees key j is j + W − 1, so the stream ends
+  // with the tile that holds it for the tile's last key (issue and the loop
+  // below both test against nqt; the new end is at least qt0 + 2)
+  const int W = WIN ? P.window : 0;
+  if (WIN) nqt = min(nqt, (kb0 + 127 + W - 1) / kKB + 1);
   const TileOff<kD> qo = tile_off<kD>(Q.st, wave, lane), go = tile_off<kD>(G.st, wave, lane);
   auto issue = [&](int it) {
     if (qt0 + it >= nqt) return;
@@ -326,6 +386,7 @@ __global__ void __launch_bounds__(kT) attn128_bwd_dkv_kernel(Attn128Params P, At
 #pragma unroll 1
     for (int qs = 0; qs < 2; ++qs) {
       if (CAUSAL && qb + 32 * qs + 31 < k0) continue;  // every query precedes every key
+      if (WIN && qb + 32 * qs > k0 + 31 + W - 1) continue;  // every query lies past every key's window
       f32x16 s = zero16(), dp = zero16();
 #pragma unroll
       for (int ks = 0; ks < kKS; ++ks) {
@@ -334,6 +395,8 @@ __global__ void __launch_bounds__(kT) attn128_bwd_dkv_kernel(Attn128Params P, At
       }
       // the mask only where some query of the slice precedes the wave's last key
       const bool diag = CAUSAL && qb + 32 * qs < k0 + 31;
+      // the window's edge only where the slice's last query lies past the first key's window
+      const bool up = WIN && qb + 32 * qs + 31 >= k0 + W;
       // rows: query qb + 32qs + (r&3) + 8(r>>2) + 4hh; column: this lane's key.
       // P goes into s, dS into dp, in place.
 #pragma unroll
@@ -347,6 +410,7 @@ __global__ void __launch_bounds__(kT) attn128_bwd_dkv_kernel(Attn128Params P, At
           const int r = 4 * g + e;
           float p = __builtin_amdgcn_exp2f(fmaf(s[r], c, -lv[e]));
           if (CAUSAL && diag) p = key > qb + rl + e ? 0.f : p;
+          if (WIN && up) p = qb + rl + e >= key + W ? 0.f : p;
           s[r] = p;
           dp[r] = p * (dp[r] - dv4[e]);  // dS (without the softmax scale)
         }
@@ -370,6 +434,9 @@ __global__ void __launch_bounds__(kT) attn128_bwd_dkv_kernel(Attn128Params P, At
   }
 }
 
+// the windowed instantiations only where the window hides something
+bool windowed(const Attn128Params& p) { return p.causal && p.window > 0 && p.window < p.T; }
+
 }  // namespace
 
 bool attn128_supported(int T) { return T > 0 && T % kKB == 0 && T <= 8192; }
@@ -377,22 +444,26 @@ bool attn128_supported(int T) { return T > 0 && T % kKB == 0 && T <= 8192; }
 void attn128_fwd(const Attn128Params& p, AttnTensor q, AttnTensor k, AttnTensor v, AttnOut o, float* lse,
                  hipStream_t s) {
   const dim3 grid(p.B * p.H, (p.T + 127) / 128);
-  if (p.causal) hipLaunchKernelGGL(attn128_fwd_kernel<true>, grid, dim3(kT), 0, s, p, q, k, v, o, lse);
+  if (windowed(p)) hipLaunchKernelGGL((attn128_fwd_kernel<true, true>), grid, dim3(kT), 0, s, p, q, k, v, o, lse);
+  else if (p.causal) hipLaunchKernelGGL(attn128_fwd_kernel<true>, grid, dim3(kT), 0, s, p, q, k, v, o, lse);
   else hipLaunchKernelGGL(attn128_fwd_kernel<false>, grid, dim3(kT), 0, s, p, q, k, v, o, lse);
 }
 
 namespace {
-template <bool CAUSAL>
+template <bool CAUSAL, bool WIN = false>
 hipError_t bwd_launch(const Attn128Params& p, AttnTensor q, AttnTensor k, AttnTensor v, AttnTensor o, AttnTensor dout,
                       const float* lse, float* delta, AttnOut dq, AttnOut dk, AttnOut dv, hipStream_t s) {
   constexpr int kLds = 2 * kStageQG;  // 65 KiB: above the 64-KiB default
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(attn128_bwd_dkv_kernel<CAUSAL>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
+  // (one static per instantiation: the windowed dK/dV kernel gets its own attribute call)
+  static const hipError_t attr =
+      hipFuncSetAttribute(reinterpret_cast<const void*>(attn128_bwd_dkv_kernel<CAUSAL, WIN>),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, kLds);
   if (attr != hipSuccess) return attr;
   const dim3 grid(p.B * p.H, (p.T + 127) / 128);
   // dQ first: it computes δ on the way and stores it for dK/dV
-  hipLaunchKernelGGL(attn128_bwd_dq_kernel<CAUSAL>, grid, dim3(kT), 0, s, p, q, k, v, dout, o, lse, delta, dq);
-  hipLaunchKernelGGL(attn128_bwd_dkv_kernel<CAUSAL>, grid, dim3(kT), kLds, s, p, q, k, v, dout, lse, delta, dk, dv);
+  hipLaunchKernelGGL((attn128_bwd_dq_kernel<CAUSAL, WIN>), grid, dim3(kT), 0, s, p, q, k, v, dout, o, lse, delta, dq);
+  hipLaunchKernelGGL((attn128_bwd_dkv_kernel<CAUSAL, WIN>), grid, dim3(kT), kLds, s, p, q, k, v, dout, lse, delta, dk,
+                     dv);
   return hipSuccess;
 }
 }  // namespace
@@ -400,6 +471,7 @@ hipError_t bwd_launch(const Attn128Params& p, AttnTensor q, AttnTensor k, AttnTe
 hipError_t attn128_bwd(const Attn128Params& p, AttnTensor q, AttnTensor k, AttnTensor v, AttnTensor o,
                        AttnTensor dout, const float* lse, float* delta, AttnOut dq, AttnOut dk, AttnOut dv,
                        hipStream_t s) {
+  if (windowed(p)) return bwd_launch<true, true>(p, q, k, v, o, dout, lse, delta, dq, dk, dv, s);
   return p.causal ? bwd_launch<true>(p, q, k, v, o, dout, lse, delta, dq, dk, dv, s)
                   : bwd_launch<false>(p, q, k, v, o, dout, lse, delta, dq, dk, dv, s);
 }

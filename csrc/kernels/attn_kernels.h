@@ -80,22 +80,31 @@ void attn_bwd(const AttnParams& p, AttnTensor q, AttnTensor k, AttnTensor v, Att
 
 // ---- head dim 128 (attention_d128.hip) ------------------------------------
 // The same tensor views with 128 channels per head ([B, T, H*128]); softmax
-// scale 1/sqrt(128); causal or not; no dropout, no key-padding mask.
+// scale 1/sqrt(128); causal or not; no dropout, no key-padding mask. Optional
+// sliding window on top of the causal mask: query i attends key j iff
+// i - window < j <= i (window keys, itself included).
 struct Attn128Params {
   int B, H, T;
   bool causal;
+  // sliding window W in keys; 0 = none. Requires causal. 0 < W < T launches
+  // the windowed instantiations, which stage and compute only the 64-key
+  // blocks of the band; W >= T is plain causal attention and launches the
+  // causal ones. (Behind causal: the kernels that carry no window code keep
+  // their instruction streams, kernel-argument offsets aside)
+  int window;
 };
 
 // T a multiple of 64, at most 8192
 bool attn128_supported(int T);
 
-// o [B, T, H*128] (strided), lse [B*H, T] fp32 (log2 domain, internal to the backward)
+// o [B, T, H*128] (strided), lse [B*H, T] fp32 (log2 domain, internal to the
+// backward; with a window it is the normaliser over the band's keys)
 void attn128_fwd(const Attn128Params& p, AttnTensor q, AttnTensor k, AttnTensor v, AttnOut o, float* lse,
                  hipStream_t s);
 
 // delta [B*H, T] fp32 workspace (written by the dQ kernel, read by dK/dV);
 // dq/dk/dv strided outputs. Returns the first launch error (the dK/dV kernel
-// asks for more than 64 KiB of LDS).
+// asks for more than 64 KiB of LDS). p.window as given to the forward.
 hipError_t attn128_bwd(const Attn128Params& p, AttnTensor q, AttnTensor k, AttnTensor v, AttnTensor o,
                        AttnTensor dout, const float* lse, float* delta, AttnOut dq, AttnOut dk, AttnOut dv,
                        hipStream_t s);

@@ -30,6 +30,12 @@ attention dropout, so a fused model with ``dropout > 0`` in training takes
 ``scaled_dot_product_attention`` for the attention core at that width (the
 rest of the block stays fused).
 
+``LlamaConfig(sliding_window=W)`` (Mistral 7B, the local layers of Gemma 2 / 3):
+query i attends keys ``i − W + 1 … i``. At head dim 128 the fused path passes
+``window=W`` to the flash attention, whose kernels visit only the key blocks
+of the band; the plain path, and the fused path at head dim 64 (whose kernels
+have no window), give ``scaled_dot_product_attention`` the equivalent bool mask.
+
 ``LlamaConfig(fp8=True)`` (opt-in, default off; fused models only): the two
 un-packed projections of every block, ``attention.wo`` and ``feed_forward.w2``,
 run their forward and data-gradient GEMMs in row-scaled fp8 (``ops/fp8.py``:
@@ -77,10 +83,13 @@ class LlamaConfig:
     norm_eps: float = 1e-6
     fp8: bool = False  # wo / w2 forward and data gradient in fp8 (fused models; module docstring)
     fp8_wgrad: bool = False  # their weight gradients in fp8 too (requires fp8)
+    sliding_window: int | None = None  # query i attends keys i - W + 1 … i (None: all preceding keys)
 
     def __post_init__(self):
         if self.fp8_wgrad and not self.fp8:
             raise ValueError("LlamaConfig: fp8_wgrad=True requires fp8=True")
+        if self.sliding_window is not None and self.sliding_window < 1:
+            raise ValueError(f"LlamaConfig: sliding_window must be >= 1 or None, got {self.sliding_window}")
 
 
 _ZERO_BIAS: dict = {}
@@ -169,27 +178,38 @@ class Attention(nn.Module):
             self.wo.wgrad = "fp8"
         self.n_head, self.dropout, self.fused = cfg.n_head, cfg.dropout, fused
         self.head_dim = C // cfg.n_head
+        self.window = cfg.sliding_window
 
     def forward(self, x, table):
         B, T, C = x.shape
         h, hd = self.n_head, self.head_dim
         p = self.dropout if self.training else 0.0
+        W = self.window
         if self.fused:
             qkv = _packed_bias_free(x, (self.wq, self.wk, self.wv))
-            # the 128-wide kernels have no dropout: that case takes the SDPA core below
-            if (attn_supported(qkv[..., :C], h, head_dim=hd) and not (hd == 128 and p > 0.0) and table.is_cuda
-                    and table.dtype == torch.float32):
+            # the 128-wide kernels have no dropout and the 64-wide ones no
+            # window: those cases take the SDPA core below
+            if (attn_supported(qkv[..., :C], h, head_dim=hd) and not (hd == 128 and p > 0.0)
+                    and not (hd == 64 and W is not None) and table.is_cuda and table.dtype == torch.float32):
                 # rotated in place on the GEMM's output, read in place by the
                 # MFMA flash attention: no head transposes, one packed gradient
                 qkv = apply_rope_qkv(qkv, h, table, inplace=True)
-                return self.wo(flash_attn_qkv(qkv, h, causal=True, dropout_p=p))
+                if W is None:
+                    return self.wo(flash_attn_qkv(qkv, h, causal=True, dropout_p=p))
+                return self.wo(flash_attn_qkv(qkv, h, causal=True, dropout_p=p, window=W))
         else:
             qkv = torch.cat([self.wq(x), self.wk(x), self.wv(x)], -1)
         q, k, v = rope_qkv_reference(qkv, h, table).split(C, dim=2)
         q = q.view(B, T, h, hd).transpose(1, 2)
         k = k.view(B, T, h, hd).transpose(1, 2)
         v = v.view(B, T, h, hd).transpose(1, 2)
-        y = F.scaled_dot_product_attention(q, k, v, dropout_p=p, is_causal=True)
+        if W is None:
+            y = F.scaled_dot_product_attention(q, k, v, dropout_p=p, is_causal=True)
+        else:
+            # the window as a bool mask (True = attend): keys i - W + 1 … i of query i
+            i = torch.arange(T, device=x.device)
+            band = (i[None, :] <= i[:, None]) & (i[None, :] > i[:, None] - W)
+            y = F.scaled_dot_product_attention(q, k, v, attn_mask=band, dropout_p=p)
         return self.wo(y.transpose(1, 2).contiguous().view(B, T, C))
 
 

@@ -21,6 +21,16 @@ functions: softmax scale 1/sqrt(128), causal or not, packed gradient as at 64.
 It has no dropout and no key-padding mask: ``dropout_p > 0`` or a ``key_mask``
 at head dim 128 raises ``ValueError``.
 
+Sliding window (head dim 128 only). ``window=W`` (an int ≥ 1) with
+``causal=True``: query i attends key j iff ``i − W < j ≤ i`` — W keys, itself
+included (Hugging Face ``sliding_window = W``, flash-attn ``window_size =
+(W − 1, 0)``; Mistral 7B, the local layers of Gemma 2 / 3). The kernels neither
+load nor compute the 64-key blocks outside the band. ``window=None`` is the
+argument's absence; ``W ≥ T`` is plain causal attention and runs the causal
+kernels (bit-identical). ``window`` without ``causal=True``, ``window < 1``, a
+non-int, or ``window`` at head dim 64 raises ``ValueError`` before any kernel
+call.
+
 Key-padding mask. ``key_mask`` has the semantics of a boolean ``attn_mask`` of
 shape [B, 1, 1, T] in ``scaled_dot_product_attention``: True means the key
 takes part. A hidden key is excluded from the row max, the softmax normaliser
@@ -90,6 +100,21 @@ def _is_d128(C: int, heads: int, dropout_p: float, key_mask) -> bool:
         raise ValueError("flash attention at head dim 128 has no key-padding mask (key_mask must be None; "
                          "head dim 64 only)")
     return True
+
+
+def _window_arg(window, causal: bool, d128: bool) -> int:
+    """``window=`` of flash_attn / flash_attn_qkv as the kernels' int (0 = none),
+    checked here, before any kernel call."""
+    if window is None:
+        return 0
+    if isinstance(window, bool) or not isinstance(window, int) or window < 1:
+        raise ValueError(f"flash attention: window must be an int >= 1 or None, got {window!r}")
+    if not causal:
+        raise ValueError("flash attention: window requires causal=True (a sliding window over the preceding keys)")
+    if not d128:
+        raise ValueError("flash attention at head dim 64 has no sliding window (window must be None; "
+                         "head dim 128 only)")
+    return min(window, 1 << 30)  # any W >= T is plain causal attention
 
 
 def _km_args(km):
@@ -181,40 +206,40 @@ def _bf16_grad(do):
 
 class _FlashAttn128Fn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, heads, causal):
-        o, lse = _C.flash_attn128_fwd(q, k, v, heads, causal)
+    def forward(ctx, q, k, v, heads, causal, window):
+        o, lse = _C.flash_attn128_fwd(q, k, v, heads, causal, window)
         ctx.save_for_backward(q, k, v, o, lse)
-        ctx.cfg = (heads, causal)
+        ctx.cfg = (heads, causal, window)
         return o
 
     @staticmethod
     def backward(ctx, do):
         q, k, v, o, lse = ctx.saved_tensors
-        heads, causal = ctx.cfg
+        heads, causal, window = ctx.cfg
         dq, dk, dv = (torch.empty_like(t, memory_format=torch.contiguous_format) for t in (q, k, v))
-        _C.flash_attn128_bwd(_bf16_grad(do), q, k, v, o, lse, heads, causal, dq, dk, dv)
-        return dq, dk, dv, None, None
+        _C.flash_attn128_bwd(_bf16_grad(do), q, k, v, o, lse, heads, causal, dq, dk, dv, window)
+        return dq, dk, dv, None, None, None
 
 
 class _FlashAttn128QKVFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, heads, causal):
+    def forward(ctx, qkv, heads, causal, window):
         C = qkv.shape[2] // 3
-        o, lse = _C.flash_attn128_fwd(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], heads, causal)
+        o, lse = _C.flash_attn128_fwd(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], heads, causal, window)
         ctx.save_for_backward(qkv, o, lse)
-        ctx.cfg = (heads, causal)
+        ctx.cfg = (heads, causal, window)
         return o
 
     @staticmethod
     def backward(ctx, do):
         qkv, o, lse = ctx.saved_tensors
-        heads, causal = ctx.cfg
+        heads, causal, window = ctx.cfg
         C = qkv.shape[2] // 3
         # the three gradients land in one packed buffer (no cat)
         dqkv = torch.empty_like(qkv, memory_format=torch.contiguous_format)
         _C.flash_attn128_bwd(_bf16_grad(do), qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], o, lse, heads, causal,
-                             dqkv[..., :C], dqkv[..., C:2 * C], dqkv[..., 2 * C:])
-        return dqkv, None, None
+                             dqkv[..., :C], dqkv[..., C:2 * C], dqkv[..., 2 * C:], window)
+        return dqkv, None, None, None
 
 
 def pack_key_mask(mask: torch.Tensor) -> torch.Tensor:
@@ -261,10 +286,14 @@ def _packed_key_mask(key_mask, B: int, T: int):
 
 def flash_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, causal: bool = False,
                dropout_p: float = 0.0, seed: int = None, key_mask: torch.Tensor = None,
-               seed_offset: torch.Tensor = None) -> torch.Tensor:
+               seed_offset: torch.Tensor = None, window: int = None) -> torch.Tensor:
     """softmax(q kᵀ / 8 [+ causal mask] [+ key mask]) → dropout(p) → · v, per head of 64;
     with ``q.shape[2] == 128 * heads``: softmax(q kᵀ / sqrt(128) [+ causal mask]) · v per
     head of 128 (no dropout, no key mask: ``ValueError``).
+
+    ``window``: sliding-window causal attention at head dim 128 (module
+    docstring): with ``causal=True``, query i attends keys ``i − window + 1 … i``.
+    None: no window. ``window >= T`` is plain causal attention.
 
     ``key_mask``: a [B, T] bool key-padding mask (True = the key takes part;
     module docstring), packed on the spot by one small kernel, or the result
@@ -287,8 +316,10 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, ca
     fresh mask. An explicit ``seed=`` without ``seed_offset=`` keeps its plain
     meaning: the mask is that seed's, frozen under capture, the same on every
     replay."""
-    if _is_d128(q.shape[2], heads, float(dropout_p), key_mask):
-        return _FlashAttn128Fn.apply(q, k, v, heads, causal)
+    d128 = _is_d128(q.shape[2], heads, float(dropout_p), key_mask)
+    win = _window_arg(window, causal, d128)
+    if d128:
+        return _FlashAttn128Fn.apply(q, k, v, heads, causal, win)
     host_seed, off = _seed_and_offset(q, float(dropout_p), seed, seed_offset)
     km = _packed_key_mask(key_mask, q.shape[0], q.shape[1])
     return _FlashAttnFn.apply(q, k, v, heads, causal, float(dropout_p), host_seed, _backward_will_run(q, k, v), km,
@@ -296,11 +327,15 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, heads: int, ca
 
 
 def flash_attn_qkv(qkv: torch.Tensor, heads: int, causal: bool = False, dropout_p: float = 0.0,
-                   seed: int = None, key_mask: torch.Tensor = None, seed_offset: torch.Tensor = None) -> torch.Tensor:
+                   seed: int = None, key_mask: torch.Tensor = None, seed_offset: torch.Tensor = None,
+                   window: int = None) -> torch.Tensor:
     """:func:`flash_attn` on the three slices of a packed [B, T, 3*H*64] (or
-    3*H*128) projection (``key_mask``, ``seed`` and ``seed_offset`` as there)."""
-    if qkv.shape[2] % 3 == 0 and _is_d128(qkv.shape[2] // 3, heads, float(dropout_p), key_mask):
-        return _FlashAttn128QKVFn.apply(qkv, heads, causal)
+    3*H*128) projection (``key_mask``, ``seed``, ``seed_offset`` and ``window``
+    as there)."""
+    d128 = qkv.shape[2] % 3 == 0 and _is_d128(qkv.shape[2] // 3, heads, float(dropout_p), key_mask)
+    win = _window_arg(window, causal, d128)
+    if d128:
+        return _FlashAttn128QKVFn.apply(qkv, heads, causal, win)
     host_seed, off = _seed_and_offset(qkv, float(dropout_p), seed, seed_offset)
     km = _packed_key_mask(key_mask, qkv.shape[0], qkv.shape[1])
     return _FlashAttnQKVFn.apply(qkv, heads, causal, float(dropout_p), host_seed, _backward_will_run(qkv), km, off)

@@ -8,6 +8,12 @@ scaled_dot_product_attention gets the same boolean mask as [B, 1, 1, T].
 ``llama-d128`` is the head-dim-128 kernel family at B8 T1024, 12 heads of 128,
 causal, no dropout (profiles/attn_d128_bench.jsonl: ``--cases llama-d128
 --iters 50 --repeat 5 --out profiles/attn_d128_bench.jsonl``).
+``mistral-swa`` is the sliding-window variant of that family at B1 T8192, 8
+heads of 128: ``window=1024`` and ``window=4096`` against the unwindowed causal
+kernels at the same shape (no SDPA column: the yardstick is our own causal
+path), the three alternating; ``*_vs_causal`` is the time ratio and
+``*_blocks_vs_causal`` the ratio of visited 64-key blocks it is to be read
+against (profiles/attn_window_bench.jsonl).
 
     python tools/attn_bench.py [--iters 10] [--graph 1] [--repeat 1] [--out FILE]
 
@@ -62,7 +68,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--cases", nargs="*", default=None,
-                    help="subset of bert gpt2 bert-nodrop gpt2-nodrop bert-pad bert-pad-full llama-d128")
+                    help="subset of bert gpt2 bert-nodrop gpt2-nodrop bert-pad bert-pad-full llama-d128 mistral-swa")
     ap.add_argument("--graph", type=int, default=1)
     ap.add_argument("--repeat", type=int, default=1)
     ap.add_argument("--out", default=None, help="append the JSON lines to this file too")
@@ -71,16 +77,44 @@ def main():
     GRAPH = bool(a.graph)
     dev = torch.device("cuda", 0)
 
-    def pair(r, key, ours, sdpa):
-        """ours / SDPA timed a.repeat times, alternating; median (+ spread)"""
-        runs = {"ours": [], "sdpa": []}
+    def rounds(r, key, fns):
+        """the variants of ``fns`` timed a.repeat times, alternating; median (+ spread)"""
+        runs = {who: [] for who in fns}
         for _ in range(a.repeat):
-            runs["ours"].append(timeit(ours, a.iters))
-            runs["sdpa"].append(timeit(sdpa, a.iters))
+            for who, fn in fns.items():
+                runs[who].append(timeit(fn, a.iters))
         for who, ts in runs.items():
             r[f"{who}_{key}_us"] = sorted(ts)[len(ts) // 2]
             if a.repeat > 1:
                 r[f"{who}_{key}_spread_us"] = max(ts) - min(ts)
+
+    def pair(r, key, ours, sdpa):
+        rounds(r, key, {"ours": ours, "sdpa": sdpa})
+
+    def emit(r):
+        line = json.dumps({kk: (round(vv, 3 if kk.endswith("_vs_causal") else 1) if isinstance(vv, float) else vv)
+                           for kk, vv in r.items()})
+        print(line, flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(line + "\n")
+
+    if not a.cases or "mistral-swa" in a.cases:
+        B, T, H, D = 1, 8192, 8, 128
+        q, k, v, do = (torch.randn(B, T, H * D, device=dev, dtype=torch.bfloat16) for _ in range(4))
+        qa, ka, va = (t.clone().requires_grad_(True) for t in (q, k, v))
+        kws = {"w1024": {"window": 1024}, "w4096": {"window": 4096}, "causal": {}}
+        r = {"case": "mistral-swa", "graph": GRAPH, "iters": a.iters, "repeat": a.repeat}
+        rounds(r, "fwd", {n: (lambda kw=kw: flash_attn(q, k, v, H, True, **kw)) for n, kw in kws.items()})
+        rounds(r, "fwdbwd", {n: (lambda kw=kw: torch.autograd.grad(flash_attn(qa, ka, va, H, True, **kw),
+                                                                   (qa, ka, va), do)) for n, kw in kws.items()})
+        # 64-key blocks a 128-query tile stages: min(T/64, 2·tile + 2) − it_lo (attention_d128.hip)
+        blocks = lambda W: sum(2 * t + 2 - max(0, 128 * t - W + 1) // 64 for t in range(T // 128))
+        for n, W in (("w1024", 1024), ("w4096", 4096)):
+            r[f"{n}_blocks_vs_causal"] = blocks(W) / blocks(T)
+            for key in ("fwd", "fwdbwd"):
+                r[f"{n}_{key}_vs_causal"] = r[f"{n}_{key}_us"] / r[f"causal_{key}_us"]
+        emit(r)
 
     for name, B, T, H, causal, p, pad, D in [("bert", 32, 512, 12, False, 0.1, None, 64),
                                              ("gpt2", 8, 1024, 12, True, 0.1, None, 64),
@@ -129,11 +163,7 @@ def main():
         pair(r, "fwdbwd", ours_fb, sdpa_fb)
         r["ours_fwd_TFps"] = fl / (r["ours_fwd_us"] * 1e-6) / 1e12
         r["ours_fwdbwd_TFps"] = 3.5 * fl / (r["ours_fwdbwd_us"] * 1e-6) / 1e12
-        line = json.dumps({kk: (round(vv, 1) if isinstance(vv, float) else vv) for kk, vv in r.items()})
-        print(line, flush=True)
-        if a.out:
-            with open(a.out, "a") as f:
-                f.write(line + "\n")
+        emit(r)
 
 
 if __name__ == "__main__":
